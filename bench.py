@@ -34,6 +34,11 @@ all-gather the decoded detections (dp.all_gather_detections: the RCCL counterpar
   split of the fp32 weights (spikes are exactly {0,1}; fp32 accumulation; as accurate as the fp32 MFMA chain,
   tools/bf16x3_numerics.hip) - the results are fp32 results, the executed MFMA work is 3x the algorithmic FLOPs.
 --precision f32: fp32 matrix cores, 3x3 conv + LIF fused over T (profiles/r1_c_pmc_final.txt).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step computed - the RPN head's per-level logits and box
+  deltas, the detector head's class logits and box deltas, the exchange payload and its counts (spike-rate workloads: the heads'
+  outputs and rate tensors) - as DIR/<name>.npy in float32 / float64, at most 64 MiB in all (larger outputs as a fixed, seeded
+  sample of their elements).  Weights and inputs are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -160,6 +165,7 @@ class Leg:
         self.det_head = S.FastRCNNPredictorSNNFull(C * 49, HD, wl["K"], wl["T_det"]).to(dev)
         self.set_precision(precision)
         self.rpn_head.spike_rates = self.det_head.spike_rates = wl["spike_rates"]
+        self.keep_outputs, self.last_outputs = False, None          # step() keeps references to its outputs (--dump-outputs)
         self.input_note = None
         if inputs == "backbone":
             self.feats, self.rois, self.input_note = self._backbone_inputs(seed, backbone_model)
@@ -181,12 +187,17 @@ class Leg:
     def _backbone_inputs(self, seed, model):
         """FPN pyramid of seeded rand images through transform + ResNet-50-FPN (random init, reference hyper-parameters);
         RoI features = MultiScaleRoIAlign of 1000 seeded boxes per image (sizes log-uniform 16..512 px)"""
+        import copy
+
         import torch
         from snn_automotive_object_detection_amd.stock.roi_align import MultiScaleRoIAlign
         wl, dev = self.wl, self.dev
         g = torch.Generator(device="cpu").manual_seed(seed)
         H, W = wl["image"]
-        images = [torch.rand((3, H, W), generator=g).to(dev) for _ in range(wl["batch"])]
+        images = [torch.rand((3, H, W), generator=g) for _ in range(wl["batch"])]
+        # on the host: the stock GPU convolutions may pick another algorithm in another process, the host ones give the same bits on
+        # every run, so the inputs (and what --dump-outputs writes) are identical from run to run
+        model = copy.deepcopy(model).cpu()
         with torch.no_grad():
             il, _ = model.transform(images)
             fmap = model.backbone(il.tensors)
@@ -199,10 +210,11 @@ class Leg:
                 b = torch.cat([ctr - size / 2, ctr + size / 2], 1)
                 b[:, 0::2] = b[:, 0::2].clamp(0, float(w))
                 b[:, 1::2] = b[:, 1::2].clamp(0, float(h))
-                props.append(b.to(dev))
+                props.append(b)
             pool = MultiScaleRoIAlign(featmap_names=["0", "1", "2", "3"], output_size=7, sampling_ratio=2)
-            rois = pool(fmap, props, il.image_sizes).contiguous()
-        del images, fmap
+            rois = pool(fmap, props, il.image_sizes).contiguous().to(dev)
+            feats = [f.to(dev) for f in feats]
+        del images, fmap, model
         note = ("FPN output of the random-init ResNet-50-FPN on seeded rand(3,%d,%d) images (transform 768/1536); RoI features = "
                 "7x7 RoIAlign of 1000 seeded boxes per image" % (H, W))
         return feats, rois, note
@@ -212,10 +224,16 @@ class Leg:
         rpn_out = self.rpn_head(self.feats)
         det_out = self.det_head(self.rois)
         if self.wl["spike_rates"]:       # the spike-rate variants return rate tensors only (faster_rcnn.py:520-618)
+            if self.keep_outputs:
+                self.last_outputs = {"rpn_logits": rpn_out[0], "rpn_bbox": rpn_out[1], "rpn_rates": rpn_out[2], "det_rates": det_out}
             return rpn_out, det_out
         cls, deltas = det_out
         payload, counts = ops.det_exchange_payload(cls, deltas, self.wl["batch"], 100)   # top-100 RoIs per image, one launch
-        return dp.all_gather_detection_tensors(payload, counts)  # no-op at world == 1
+        out = dp.all_gather_detection_tensors(payload, counts)  # no-op at world == 1
+        if self.keep_outputs:            # what a caller of the step receives (references only)
+            self.last_outputs = {"rpn_logits": rpn_out[0], "rpn_bbox": rpn_out[1], "det_cls": cls, "det_bbox": deltas,
+                                 "payload": out[0], "counts": out[1]}
+        return out
 
     def step_local(self):
         """the same step without the collective (side legs that only rank 0 runs)"""
@@ -346,6 +364,46 @@ def timed_steps(leg, steps, warmup, fence):
         leg.step()
     fence()
     return time.perf_counter() - t0
+
+
+DUMP_BYTES_MAX = 64 << 20                                        # --dump-outputs: at most 64 MiB of .npy payload
+DUMP_SAMPLE_SEED = 0
+
+
+def host_outputs(tree, name=""):
+    """flatten nested dicts / lists / tuples of tensors into [(name, host numpy array)]: list entries get _<index>, floating
+    results float32 (float64 stays float64), integer / bool results float64 (exact)"""
+    import numpy as np
+    import torch
+    if isinstance(tree, dict):
+        return [kv for k, v in tree.items() for kv in host_outputs(v, "%s_%s" % (name, k) if name else k)]
+    if isinstance(tree, (list, tuple)):
+        return [kv for i, v in enumerate(tree) for kv in host_outputs(v, "%s_%d" % (name, i))]
+    t = tree.detach().cpu()
+    dt = np.float64 if (t.dtype == torch.float64 or not t.dtype.is_floating_point) else np.float32
+    return [(name, np.ascontiguousarray(t.to(torch.float64 if dt is np.float64 else torch.float32).numpy()))]
+
+
+def dump_outputs(arrays, out_dir, max_bytes=DUMP_BYTES_MAX):
+    """write [(name, array)] as out_dir/<name>.npy.  If they exceed max_bytes together, the largest arrays are replaced by a fixed,
+    seeded sample of their flattened elements (sorted indices, the same for every run on the same shapes); smaller arrays stay whole.
+    Returns {name: {"shape", "dtype", "sampled"}} (sampled: number of elements kept, None when the array is whole)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info, left = {}, max_bytes
+    order = sorted(range(len(arrays)), key=lambda i: (arrays[i][1].nbytes, i))        # smallest first: they are kept whole
+    for j, i in enumerate(order):
+        name, a = arrays[i]
+        share = left // (len(order) - j)                                               # an even share of what is left
+        keep = a.size if a.nbytes <= share else share // a.itemsize
+        flat = a
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=keep, replace=False))
+            flat = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), flat)
+        left -= flat.nbytes
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": None if keep == a.size else int(keep)}
+    return info
 
 
 NOMINAL_CLOCK_GHZ = 2.4                                          # MI355X_MICROARCH.md chip table: the clock the 2.5 PF / 5 PF peaks are quoted at
@@ -701,7 +759,12 @@ def main():
     ap.add_argument("--sweep-t", action="store_true", help="only the throughput-vs-T grid (T_rpn 4..12, T_det 8..16) besides the headline")
     ap.add_argument("--no-dp-e2e", action="store_true", help="skip the whole-model data-parallel leg (config[3])")
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the held-clock probe (runs under rocprofv3 --pmc, where kernels are serialised and the probe says nothing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (head outputs, exchange payload) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MiB in all: larger outputs as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- stand-alone multi-rank launch: start the ranks BEFORE anything initialises the GPU in this process ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -752,7 +815,12 @@ def main():
     def fence_local():                                           # legs that run on one rank only
         torch.cuda.synchronize()
 
+    leg.keep_outputs = bool(args.dump_outputs)
     dt = timed_steps(leg, args.steps, args.warmup, fence)
+    dumped = None
+    if args.dump_outputs and rank == 0:                          # copied to the host now: the side legs below run the same modules again
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(host_outputs(leg.last_outputs), args.dump_outputs)}
+    leg.keep_outputs, leg.last_outputs = False, None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev if dp.backend_name() != "gloo" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -828,6 +896,8 @@ def main():
         "heads_tflops": round((rpn_fl + det_fl) / ((bd["rpn_head"] + bd["det_head"]) * 1e-3) / 1e12, 2),
         "exchange": exchange,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     enc_rpn = out["roofline"].get("encoders", {}).get("rpn")
     if enc_rpn and enc_rpn.get("algorithmic_hbm_bytes") and bd["rpn_encode"] > 0:      # (the RPN encoder is also timed live: stage 1 of the head by itself)
         enc_rpn["live_ms"] = round(bd["rpn_encode"], 4)

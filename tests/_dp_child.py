@@ -21,7 +21,7 @@ counts = torch.tensor([rank + 1, 0], dtype=torch.int32)
 g_p, g_c = dp.all_gather_detection_tensors(payload, counts)
 assert g_p.shape == (2 * world, 4, 6) and g_c.tolist() == [c for r in range(world) for c in (r + 1, 0)]
 assert all(float(g_p[2 * r].min()) == float(r) for r in range(world))
-dist.barrier()
+dist.monitored_barrier()                                   # (gloo, host only: dist.barrier() asks for the accelerator, which opens the GPU)
 dist.destroy_process_group()
 if rank == 0:
     print("LAUNCH_OK world=%d" % world, flush=True)

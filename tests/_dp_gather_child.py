@@ -39,7 +39,7 @@ for kwargs in ({}, {"images_per_rank": (n_images + world - 1) // world}):
             assert g_[k].dtype == e[k].dtype and torch.equal(g_[k], e[k]), (i, k)
 plain = dp.all_gather_detections(dets, max_det=16, device=torch.device("cpu"))          # without extras: the three base keys only
 assert len(plain) == n_images and all(set(d.keys()) == {"boxes", "scores", "labels"} for d in plain)
-dist.barrier()
+dist.monitored_barrier()                                   # (gloo, host only: dist.barrier() asks for the accelerator, which opens the GPU)
 dist.destroy_process_group()
 if rank == 0:
     print("GATHER_OK world=%d images=%d" % (world, n_images), flush=True)

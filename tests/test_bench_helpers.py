@@ -70,3 +70,31 @@ def test_committed_traffic_is_quoted_only_for_the_tree_it_was_collected_on(tmp_p
     assert bench.load_committed_traffic(str(tmp_path / "missing.json"), doc["source_digest"], "cityscapes", "bf16x3") == (None, None, {})
     # the committed file belongs to the committed tree (fails when a kernel source changes without a new evidence run: re-run tools/r6_final.sh + r6_collect.sh)
     assert doc["source_digest"] == build.source_digest(), "profiles/r6_traffic.json is stale against csrc/ + include/"
+
+
+def test_dump_outputs_names_dtypes_and_the_size_cap(tmp_path):
+    """--dump-outputs: nested outputs flatten to <name>.npy in float32 / float64 (integers exact); past the byte cap the largest arrays
+    become a seeded sample of their elements, the same on every run, and the small ones stay whole"""
+    big = torch.arange(1 << 16, dtype=torch.float32).reshape(256, 256)
+    tree = {"rpn_logits": [torch.ones(2, 3, 4, 5), big], "counts": torch.tensor([7, 1 << 40], dtype=torch.int64),
+            "rates": torch.full((3,), 0.5, dtype=torch.float64), "spikes": torch.tensor([True, False])}
+    arrays = bench.host_outputs(tree)
+    assert [n for n, _ in arrays] == ["rpn_logits_0", "rpn_logits_1", "counts", "rates", "spikes"]
+    assert {n: a.dtype for n, a in arrays} == {"rpn_logits_0": np.float32, "rpn_logits_1": np.float32, "counts": np.float64,
+                                               "rates": np.float64, "spikes": np.float64}
+    cap = 64 << 10                                                                # 64 KiB: the 256 KiB array cannot stay whole
+    info = bench.dump_outputs(arrays, str(tmp_path / "a"), max_bytes=cap)
+    again = bench.dump_outputs(bench.host_outputs(tree), str(tmp_path / "b"), max_bytes=cap)
+    assert info == again and info["rpn_logits_1"]["shape"] == [256, 256] and info["rpn_logits_1"]["sampled"]
+    total = 0
+    for name, a in arrays:
+        x = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert x.dtype in (np.float32, np.float64)
+        assert np.array_equal(x, np.load(str(tmp_path / "b" / (name + ".npy"))))
+        total += x.nbytes
+        if info[name]["sampled"] is None:
+            assert np.array_equal(x, a)
+        else:                                                                     # sorted distinct elements of the original
+            assert x.size == info[name]["sampled"] and np.all(np.diff(x) > 0) and np.isin(x, a).all()
+    assert total <= cap
+    assert np.load(str(tmp_path / "a" / "counts.npy")).tolist() == [7.0, float(1 << 40)]

@@ -43,7 +43,7 @@ def _worker(rank, world, port, n_images, q, max_det=8):
         ok &= torch.equal(d["scores"], e["scores"][:k]) and torch.equal(d["labels"], e["labels"][:k])
         ok &= d["labels"].dtype == torch.int64
     q.put((rank, bool(ok), list(mine)))
-    dist.barrier()
+    dist.monitored_barrier()                              # (gloo, host only: dist.barrier() asks for the accelerator, which opens the GPU)
     dist.destroy_process_group()
 
 
