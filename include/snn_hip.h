@@ -200,6 +200,41 @@ int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_leve
                                     uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls, float* sum_bbox,
                                     void* workspace, size_t workspace_bytes, snn_stream_t stream);
 
+/* ---- any-time readouts: every T' of a time-step sweep from one pass ----
+ * steps: host array T'_0 < ... < T'_{n-1}, each in [1, SNN_MAX_STEPS], n_steps in [1, SNN_MAX_STEPS]; the pass runs at
+ * T = steps[n_steps - 1] and takes the workspace of the T call (snn_rpn_head_workspace_bytes / snn_det_head_workspace_bytes at T).
+ * Every LIF state at step t depends only on steps < t and every forward starts from zero state, so the outputs of a T'-step
+ * forward are the first T' steps of the T pass folded with the LI cell's kappa at T'.
+ * Outputs are stacked by readout: RPN out_logits [n][P][A], out_bbox [n][P][4A] (sums alike, nullable as a pair), spike_counts
+ * [n][n_levels][max_N] (nullable); detector out_cls [n][R][K], out_bbox [n][R][K4] (sums alike), spk6_count / spk7_count [n][R]
+ * (nullable as a pair).  Finished rate rows: snn_rpn_rates / snn_det_rates with T = T'_j on readout j's slices.
+ * Equality contract:
+ *   - readout j is bit-identical to snn_li_heads at T'_j on the first T'_j spike planes of the same pass, and its counts are the
+ *     popcounts of those planes; the readout at T' = T is bit-identical to the plain forward at T (outputs, sums, counts);
+ *   - against a standalone forward at T' < T: the spike planes of steps < T' are identical wherever both runs take the same conv / fc6
+ *     launch (the structured-sparse launches: every accumulator sees the same instructions in the same order, period planes of later
+ *     steps add nothing to earlier ones); where the standalone takes another launch (dense conv at T' <= 4, SNN_SPARSE=0, ...) its
+ *     currents may round differently and a neuron at its threshold may flip: equal up to those ties.
+ * Bad arguments return -1 (snn_last_error) before any device work; no host synchronisation. */
+int snn_li_heads_readouts(const uint32_t* spk, size_t spk_stride, const int* steps, int n_steps, int M, int K,
+                          const float* w_heads_packed, int NA, int NB, const snn_params* p_host, float* out_a, float* out_b,
+                          float* sum_a, float* sum_b, snn_stream_t stream);
+int snn_rpn_head_forward_readouts(const snn_rpn_level* levels_host, int n_levels, int C, int A, const int* steps, int n_steps,
+                                  const snn_params* p_host, const void* w_shared_packed, const float* w_heads_packed,
+                                  float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                  float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+int snn_det_head_forward_readouts(const float* x, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps,
+                                  const snn_params* p_host, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                  const float* w_heads_packed, float* out_cls, float* out_bbox,
+                                  uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls, float* sum_bbox,
+                                  void* workspace, size_t workspace_bytes, snn_stream_t stream);
+int snn_det_head_forward_roialign_readouts(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+                                           const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4,
+                                           const int* steps, int n_steps, const snn_params* p_host, const void* w6_packed,
+                                           int w6_inner, const void* w7_packed, const float* w_heads_packed, float* out_cls,
+                                           float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls,
+                                           float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+
 /* ---- finished spike-rate tensors of the two spike-rate variants (rpn.py:171-195, faster_rcnn.py:568-618) from the raw side
  * outputs above: rows (rate, "FLOPs") as float32, what the reference hstacks per layer.
  *   snn_rpn_rates: rates[n_levels][3][max_N][2]; [l][0] = shared-LIF spikes / (T*C*H*W) with 9*H*W*C*C, [l][1] / [l][2] = mean

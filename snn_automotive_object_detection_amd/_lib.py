@@ -115,6 +115,15 @@ SYMBOLS = {
     "snn_det_head_forward_roialign_k": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_void_p] + [C.c_int] * 5 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +
                                         [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_li_heads_readouts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.POINTER(snn_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream]),
+    "snn_rpn_head_forward_readouts": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                C.POINTER(snn_params)] + [C.c_void_p] * 8 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_readouts": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.POINTER(snn_params),
+                                                C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_roialign_readouts": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.POINTER(snn_params),
+                                                         C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
     "snn_packed_linear_mx_words": (C.c_size_t, [C.c_int, C.c_int]),
     "snn_packed_conv3x3_mx_words": (C.c_size_t, [C.c_int, C.c_int]),
     "snn_pack_linear_weight_mx": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),

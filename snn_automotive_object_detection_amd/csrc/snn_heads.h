@@ -445,6 +445,348 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit(const LiHeadsArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// K5b / K5c with several readouts (any-time outputs of a time-step sweep).  The LIF states of steps < T' do not depend on
+// the later steps, so a T' < T readout of a T-step pass is  mem_T' = sum_{t < T'} kappa^(T')[t] * (spk_t . W)  over the same
+// per-step products acc[t] the single-readout kernels form.  Readout j folds them with its own kappa^(T'_j) (li_kappa at T'_j,
+// zero beyond T'_j): the same fmaf chain, t ascending, as k_li_heads_mfma / k_li_heads_ksplit run at T'_j (steps past T'_j only
+// add fmaf(0, acc, o) = o), so every readout is bit-identical to a single-readout launch at T'_j on the same planes.
+// The products of a group are computed once; a launch holds up to RB readouts beside them in registers (RB * NT * 4 per
+// membrane, x 2 with the time sums), and more readouts run as further launches over the steps they need.  Separate kernels: the
+// single-readout instances keep their instruction streams.
+// ------------------------------------------------------------------------------------------------
+#define LIH_RO_MAX 8
+struct LiReadoutArgs {
+    LiHeadsArgs h;                                 // h.T = last readout of this launch; h.kap unused; out / sum = readout 0 of the launch
+    unsigned long long ro_stride_a, ro_stride_b;   // elements from one readout's out_a / sum_a (out_b / sum_b) to the next's
+    int n_ro;                                      // readouts of this launch (<= RB)
+    int steps[LIH_RO_MAX];                         // their T'
+    Kappa kap[LIH_RO_MAX];                         // li_kappa(p, T'_j)
+};
+// readouts per launch: what fits beside the time group's accumulators without spilling (tests/test_code_object.py)
+// (half as many with the time sums: k_li_heads_ksplit_ro<1, 8, true> spilled 2.4 KB per lane)
+#define LIH_RO_B(nt, s) (((nt) <= 2 ? 8 : 4) / ((s) ? 2 : 1))
+
+// the epilogue of a time group: readout j accumulates kappa_j[t] * acc[t] in t order (a block-uniform skip once tg0 >= T'_j)
+template <int TN, int NT, int RB, bool S>
+__device__ __forceinline__ void lih_ro_fold(const LiReadoutArgs& a, const int tg0, const f32x4 (&acc)[TN][NT], f32x4 (&o_last)[RB][NT],
+                                            f32x4 (&o_sum)[RB][NT]) {
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+        if (j >= a.n_ro || tg0 >= a.steps[j]) continue;
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+            const int ti = min(tg0 + t, a.h.T - 1);     // (steps past the group's count: their accumulators are zero)
+            const float kl = a.kap[j].last[ti], ks = a.kap[j].sum[ti];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    o_last[j][nt][r] = fmaf(kl, acc[t][nt][r], o_last[j][nt][r]);
+                    if (S) o_sum[j][nt][r] = fmaf(ks, acc[t][nt][r], o_sum[j][nt][r]);
+                }
+        }
+    }
+}
+
+// lane holds rows lg*4 + r, output column nt*16 + lr
+template <int NT, bool S>
+__device__ __forceinline__ void lih_ro_store(const LiReadoutArgs& a, int j, int m0, int lg, int lr, const f32x4 (&ol)[NT], const f32x4 (&os)[NT]) {
+    const LiHeadsArgs& h = a.h;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int c = h.col0 + nt * 16 + lr;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + lg * 4 + r;
+            if (m >= h.M) continue;
+            if (c < h.NA) {
+                const size_t o = (size_t)j * a.ro_stride_a + (size_t)m * h.NA + c;
+                h.out_a[o] = ol[nt][r];
+                if (S) h.sum_a[o] = os[nt][r];
+            } else if (c < h.NA + h.NB) {
+                const size_t o = (size_t)j * a.ro_stride_b + (size_t)m * h.NB + (c - h.NA);
+                h.out_b[o] = ol[nt][r];
+                if (S) h.sum_b[o] = os[nt][r];
+            }
+        }
+    }
+}
+
+template <int NT, int RB, bool S>
+__global__ __launch_bounds__(256) void k_li_heads_mfma_ro(const LiReadoutArgs ra) {
+    const LiHeadsArgs& a = ra.h;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const lut = smem;                           // 4 KB
+    unsigned char* const bbase = smem + G3_LUT_BYTES;          // [chunk slot][3][NOp][64 B]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
+    const int NOp = a.NOp, Kc = a.Kw;
+    const uint32_t slot_bytes = 3u * NOp * 64u;
+    {
+        uint4 q;
+        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
+        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
+    }
+    auto stage = [&](int kc, int slot) {                       // as k_li_heads_mfma
+        unsigned char* dst = bbase + (size_t)slot * slot_bytes;
+        for (int item = tid; item < 16 * NOp; item += 256) {
+            const int n = item % NOp, kp = item / NOp;
+            const float* src = a.wT + (size_t)(32 * kc + 2 * kp) * a.ldw + a.col0 + n;
+            uint32_t pl[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float w = src[(size_t)h * a.ldw];
+                const uint16_t hi = f2bf_rn(w);
+                const float r1 = __fsub_rn(w, bf2f(hi));
+                const uint16_t mid = f2bf_rn(r1);
+                const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
+                pl[0] |= (uint32_t)hi << (16 * h); pl[1] |= (uint32_t)mid << (16 * h); pl[2] |= (uint32_t)lo << (16 * h);
+            }
+            const int off = n * 64 + ((((kp >> 2) ^ G3_SWZ(n)) << 4) | ((kp & 3) << 2));
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint32_t*>(dst + q * NOp * 64 + off) = pl[q];
+        }
+    };
+    if (a.resident)
+        for (int kc = 0; kc < Kc; ++kc) stage(kc, kc);
+    __syncthreads();
+    const unsigned char* const b_rd = bbase + lr * 64 + ((lg ^ G3_SWZ(lr)) << 4);
+    for (int g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+        const int m0 = (g * 4 + wave) * 16;
+        const int mrow = min(m0 + lr, a.M - 1);                 // rows past M: recomputed, never stored
+        const uint32_t* wsrc = a.spk + (size_t)mrow * (a.half_split ? 4 : a.Kw);
+        f32x4 o_last[RB][NT], o_sum[RB][NT];
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) { o_last[j][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; o_sum[j][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        auto group = [&](auto tn_c, const int tg0, const int tn) __attribute__((always_inline)) {
+            constexpr int TN = decltype(tn_c)::value;
+            f32x4 acc[TN][NT];
+#pragma unroll
+            for (int t = 0; t < TN; ++t)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            auto chunk = [&](int kc, const uint32_t (&w_cur)[TN]) {
+                const unsigned char* bs = b_rd + (size_t)(a.resident ? kc : (kc & 1)) * slot_bytes;
+                bf16x8 b[3][NT];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        b[pl][nt] = *reinterpret_cast<const bf16x8*>(bs + (pl * NOp + nt * 16) * 64);
+#pragma unroll
+                for (int t = 0; t < TN; ++t) {
+                    const bf16x8 af = *reinterpret_cast<const bf16x8*>(lut + (__builtin_amdgcn_ubfe(w_cur[t], lg8, 8) << 4));
+#pragma unroll
+                    for (int pl = 2; pl >= 0; --pl)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+                            acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[pl][nt], acc[t][nt], 0, 0, 0);
+                }
+            };
+            if (a.resident && Kc == 8) {
+                uint4 wl[TN][2];
+#pragma unroll
+                for (int t = 0; t < TN; ++t) {
+                    const uint4* q = reinterpret_cast<const uint4*>(wsrc + (size_t)(tg0 + (t < tn ? t : 0)) * a.spk_stride);
+                    wl[t][0] = q[0]; wl[t][1] = a.half_split ? q[(size_t)a.M] : q[1];
+                    if (t >= tn) { wl[t][0] = uint4{0u, 0u, 0u, 0u}; wl[t][1] = uint4{0u, 0u, 0u, 0u}; }
+                }
+#pragma unroll
+                for (int kc = 0; kc < 8; ++kc) {
+                    uint32_t w_cur[TN];
+#pragma unroll
+                    for (int t = 0; t < TN; ++t) {
+                        const uint4 v = wl[t][kc >> 2];
+                        w_cur[t] = (kc & 3) == 0 ? v.x : (kc & 3) == 1 ? v.y : (kc & 3) == 2 ? v.z : v.w;
+                    }
+                    chunk(kc, w_cur);
+                }
+            } else {
+                uint32_t w_nxt[TN];
+#pragma unroll
+                for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride] : 0u;
+                if (!a.resident) { stage(0, 0); __syncthreads(); }
+                for (int kc = 0; kc < Kc; ++kc) {
+                    uint32_t w_cur[TN];
+#pragma unroll
+                    for (int t = 0; t < TN; ++t) w_cur[t] = w_nxt[t];
+                    if (kc + 1 < Kc) {
+#pragma unroll
+                        for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride + kc + 1] : 0u;
+                        if (!a.resident) stage(kc + 1, (kc + 1) & 1);
+                    }
+                    chunk(kc, w_cur);
+                    if (!a.resident) __syncthreads();
+                }
+            }
+            lih_ro_fold<TN, NT, RB, S>(ra, tg0, acc, o_last, o_sum);
+        };
+        for (int tg0 = 0; tg0 < a.T; tg0 += LIH_TG) {
+            const int tn = min(LIH_TG, a.T - tg0);              // block-uniform
+            if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
+            else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
+            else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
+            else group(std::integral_constant<int, 1>{}, tg0, tn);
+        }
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+            if (j < ra.n_ro) lih_ro_store<NT, S>(ra, j, m0, lg, lr, o_last[j], o_sum[j]);
+    }
+}
+
+template <int NT, int RB, bool S>
+__global__ __launch_bounds__(256) void k_li_heads_ksplit_ro(const LiReadoutArgs ra) {
+    const LiHeadsArgs& a = ra.h;
+    constexpr int TM = LIH_KS_TM(NT);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const lut = smem;                           // 4 KB
+    f32x4* const red = reinterpret_cast<f32x4*>(smem + G3_LUT_BYTES);      // [4 waves][2][NT][64 lanes], one readout at a time
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
+    const int Kc = a.Kw, T = a.T;
+    {
+        uint4 q;
+        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
+        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
+    }
+    __syncthreads();
+    const int m0 = blockIdx.x * 16;
+    const int mrow = min(m0 + lr, a.M - 1);                    // rows past M: recomputed, never stored
+    const uint32_t* wsrc = a.spk + (size_t)mrow * a.Kw;
+    const int c0 = wave * Kc / 4, c1 = (wave + 1) * Kc / 4;    // this wave's chunks
+    const float* const wlane = a.wT + (size_t)lg8 * a.ldw + a.col0 + lr;
+    f32x4 o_last[RB][NT], o_sum[RB][NT];
+#pragma unroll
+    for (int j = 0; j < RB; ++j)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) { o_last[j][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; o_sum[j][nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    auto group = [&](auto tn_c, const int tg0, const int tn) __attribute__((always_inline)) {
+        constexpr int TN = decltype(tn_c)::value;
+        f32x4 acc[TN][NT];
+#pragma unroll
+        for (int t = 0; t < TN; ++t)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float wf[NT][8];
+        uint32_t w_nxt[TN];
+        auto request = [&](int kc) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) wf[nt][j] = wlane[(size_t)(32 * kc + j) * a.ldw + nt * 16];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride + kc] : 0u;
+        };
+        if (c0 < c1) request(c0);
+        for (int kc = c0; kc < c1; ++kc) {
+            bf16x8 b[3][NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float w = wf[nt][j];
+                    const uint16_t hi = f2bf_rn(w);
+                    const float r1 = __fsub_rn(w, bf2f(hi));
+                    const uint16_t mid = f2bf_rn(r1);
+                    const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
+                    b[0][nt][j] = (short)hi; b[1][nt][j] = (short)mid; b[2][nt][j] = (short)lo;
+                }
+            uint32_t w_cur[TN];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) w_cur[t] = w_nxt[t];
+            if (kc + 1 < c1) request(kc + 1);
+#pragma unroll
+            for (int t = 0; t < TN; ++t) {
+                const bf16x8 af = *reinterpret_cast<const bf16x8*>(lut + (__builtin_amdgcn_ubfe(w_cur[t], lg8, 8) << 4));
+#pragma unroll
+                for (int pl = 2; pl >= 0; --pl)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[pl][nt], acc[t][nt], 0, 0, 0);
+            }
+        }
+        lih_ro_fold<TN, NT, RB, S>(ra, tg0, acc, o_last, o_sum);
+    };
+    for (int tg0 = 0; tg0 < T; tg0 += TM) {
+        const int tn = min(TM, T - tg0);                        // block-uniform
+        if (tn > 8) group(std::integral_constant<int, TM>{}, tg0, tn);
+        else if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
+        else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
+        else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
+        else group(std::integral_constant<int, 1>{}, tg0, tn);
+    }
+    // per readout: the four waves' partial chains meet in LDS and are added in wave order, as in k_li_heads_ksplit
+#pragma unroll
+    for (int j = 0; j < RB; ++j) {
+        if (j >= ra.n_ro) break;                               // block-uniform
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            red[((wave * 2 + 0) * NT + nt) * 64 + lane] = o_last[j][nt];
+            red[((wave * 2 + 1) * NT + nt) * 64 + lane] = o_sum[j][nt];
+        }
+        __syncthreads();
+        if (wave == 0) {
+            f32x4 ol[NT], os[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                ol[nt] = red[(0 * NT + nt) * 64 + lane]; os[nt] = red[(1 * NT + nt) * 64 + lane];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const f32x4 pl = red[((w * 2 + 0) * NT + nt) * 64 + lane], ps = red[((w * 2 + 1) * NT + nt) * 64 + lane];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { ol[nt][r] = __fadd_rn(ol[nt][r], pl[r]); os[nt][r] = __fadd_rn(os[nt][r], ps[r]); }
+                }
+            }
+            lih_ro_store<NT, S>(ra, j, m0, lg, lr, ol, os);
+        }
+        __syncthreads();
+    }
+}
+
+// spike counts of every readout: per image of one level, over the planes t < T'_j (blockIdx.x = image, blockIdx.y = slice of
+// the image's words; words at w[i] and, for planes in blocks of four words, w[i + half_off]).  counts[j * ro_stride + image],
+// zeroed by the caller; integer atomics, so the result does not depend on the order.
+struct StepList { int n; int steps[SNN_MAX_STEPS]; };
+__global__ __launch_bounds__(256) void k_count_spikes_ro(const uint32_t* __restrict__ spk, unsigned long long spk_stride,
+                                                         unsigned long long half_off, int words_per_image, const StepList st,
+                                                         unsigned long long* __restrict__ counts, unsigned long long ro_stride) {
+    __shared__ unsigned long long part[4];
+    unsigned long long sum = 0;
+    int j = 0;
+    for (int t = 0; t < st.steps[st.n - 1]; ++t) {
+        const uint32_t* src = spk + (size_t)t * spk_stride + (size_t)blockIdx.x * words_per_image;
+        for (int i = blockIdx.y * 256 + threadIdx.x; i < words_per_image; i += gridDim.y * 256)
+            sum += __popc(src[i]) + (half_off ? __popc(src[i + half_off]) : 0);
+        if (t + 1 == st.steps[j]) {                            // block-uniform
+            unsigned long long s = sum;
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+            if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+            __syncthreads();
+            if (threadIdx.x == 0) atomicAdd(&counts[(size_t)j * ro_stride + blockIdx.x], part[0] + part[1] + part[2] + part[3]);
+            __syncthreads();
+            ++j;
+        }
+    }
+}
+
+// ... per row (detector RoIs: lif6 / lif7), planes row-major [T][R][Nw] or word-major [T][Nw][R]: counts[j * R + r]
+__global__ __launch_bounds__(256) void k_count_rows_ro(const uint32_t* __restrict__ spk, unsigned long long spk_stride, int R, int Nw,
+                                                       int word_major, const StepList st, uint32_t* __restrict__ counts) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    uint32_t sum = 0;
+    int j = 0;
+    for (int t = 0; t < st.steps[st.n - 1]; ++t) {
+        const uint32_t* src = spk + (size_t)t * spk_stride;
+        for (int w = 0; w < Nw; ++w) sum += __popc(word_major ? src[(size_t)w * R + r] : src[(size_t)r * Nw + w]);
+        if (t + 1 == st.steps[j]) counts[(size_t)(j++) * R + r] = sum;
+    }
+}
+
 // spikes per image of one level, counted from the bit-planes (spike-rate mode of the bf16x3 path): blockIdx.x = image,
 // blockIdx.y = slice of the image's words; integer atomics, so the result does not depend on the order.
 // counts must be zeroed by the caller.

@@ -1542,15 +1542,23 @@ static bool li_heads_reads_split(int K, int NA, int NB) {
     return Kw == 8 && NOp <= 64 && (size_t)Kw * 3 * NOp * 64 <= 96 * 1024 && (force == 0 || force == 2);
 }
 
+// which kernel takes columns col0 .. col0 + NOp - 1 of the heads: 3 k_li_heads_ksplit, 2 k_li_heads_mfma, 1 k_li_heads (fp32 VALU)
+static int li_heads_kind(int Kw, int NOp, int force) {
+    // matrix-core kernel where all of W (as three bf16 planes) stays resident in LDS; the streamed form is latency
+    // bound on small row counts (detector heads: 164 us against 88 us for the VALU kernel) and only runs when forced
+    const bool fits = (size_t)Kw * 3 * NOp * 64 <= 96 * 1024;
+    if (NOp <= 64 && Kw >= 4 && (force ? force == 3 : !fits)) return 3;
+    if (NOp <= 64 && (force ? force == 2 : fits)) return 2;
+    return 1;
+}
+
 // columns col0 .. col0 + NOp - 1 (NOp a multiple of 16, <= 64 for the matrix-core kernels, <= 256 for the VALU kernel) of the heads
 static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, int Kw, const float* w_heads_packed, int NA, int NB,
                          const Kappa& kap, float* out_a, float* out_b, float* sum_a, float* sum_b, bool half_split, int force,
                          int ldw, int col0, int NOp, hipStream_t s) {
-    // matrix-core kernel where all of W (as three bf16 planes) stays resident in LDS; the streamed form is latency
-    // bound on small row counts (detector heads: 164 us against 88 us for the VALU kernel) and only runs when forced
-    const bool fits = (size_t)Kw * 3 * NOp * 64 <= 96 * 1024;
+    const int kind = li_heads_kind(Kw, NOp, force);
     // W too large for LDS: one work-group per 16 rows, the reduction split over its 4 waves ("ksplit" forces it)
-    if (NOp <= 64 && Kw >= 4 && (force ? force == 3 : !fits)) {
+    if (kind == 3) {
         LiHeadsArgs a;
         memset(&a, 0, sizeof(a));
         a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
@@ -1565,7 +1573,7 @@ static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, i
         SNN_CHECK_LAUNCH("k_li_heads_ksplit");
         return 0;
     }
-    if (NOp <= 64 && (force ? force == 2 : fits)) {
+    if (kind == 2) {
         LiHeadsArgs a;
         memset(&a, 0, sizeof(a));
         a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
@@ -1644,6 +1652,120 @@ int snn_li_heads(const uint32_t* spk, size_t spk_stride, int T, int M, int K, co
                  int NA, int NB, const snn_params* p, float* out_a, float* out_b, float* sum_a, float* sum_b,
                  snn_stream_t s) {
     return li_heads_impl(spk, spk_stride, T, M, K, w_heads_packed, NA, NB, p, out_a, out_b, sum_a, sum_b, false, s);
+}
+
+// ---- any-time readouts (time-step sweeps) ----------------------------------------------------------
+// a readout set: T'_0 < ... < T'_{n-1} in [1, SNN_MAX_STEPS]; the pass runs at T = T'_{n-1}
+static int check_steps(const int* steps, int n, const char* who) {
+    if (!steps) return fail(-1, "%s: null step list", who);
+    if (n < 1 || n > SNN_MAX_STEPS) return fail(-1, "%s: %d steps in the readout list (1 .. %d)", who, n, SNN_MAX_STEPS);
+    for (int j = 0; j < n; ++j) {
+        if (steps[j] < 1 || steps[j] > SNN_MAX_STEPS) return fail(-1, "%s: steps[%d] = %d outside [1, %d]", who, j, steps[j], SNN_MAX_STEPS);
+        if (j && steps[j] <= steps[j - 1]) return fail(-1, "%s: steps must be strictly increasing (steps[%d] = %d after %d)", who, j, steps[j], steps[j - 1]);
+    }
+    return 0;
+}
+static StepList step_list(const int* steps, int n) {
+    StepList st;
+    memset(&st, 0, sizeof(st));
+    st.n = n;
+    for (int j = 0; j < n; ++j) st.steps[j] = steps[j];
+    return st;
+}
+
+// outputs [n][M][NA] / [n][M][NB] (sums alike): readout j = the single-readout heads at T'_j on the first T'_j planes, bit for bit.
+// Matrix-core kernels: one launch per block of up to RB readouts, from the last block down (the first launch covers the longest
+// readouts, a remainder block the shortest), each over the steps its last readout needs.  fp32 VALU kernel: one launch per readout.
+extern "C++" template <int NT, bool S>
+static int li_heads_ro_launch(bool ksplit, const LiHeadsArgs& base, const snn_params* p, const int* steps, int n, unsigned long long st_a,
+                              unsigned long long st_b, size_t lds, hipStream_t s) {
+    constexpr int RB = LIH_RO_B(NT, S);
+    const void* kern = ksplit ? (const void*)k_li_heads_ksplit_ro<NT, RB, S> : (const void*)k_li_heads_mfma_ro<NT, RB, S>;
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    int grid = ksplit ? cdiv(base.M, 16) : base.n_groups;
+    if (!ksplit && base.resident) {                            // persistent work-groups, as k_li_heads_mfma
+        int v = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v <= 0) v = 1;
+        grid = min(base.n_groups, v * g3_slots());
+    }
+    for (int hi = n; hi > 0; hi -= RB) {
+        const int lo = max(0, hi - RB);
+        LiReadoutArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.h = base;
+        ra.h.T = steps[hi - 1];
+        ra.h.out_a = base.out_a + lo * st_a; ra.h.out_b = base.out_b + lo * st_b;
+        if (S) { ra.h.sum_a = base.sum_a + lo * st_a; ra.h.sum_b = base.sum_b + lo * st_b; }
+        ra.ro_stride_a = st_a; ra.ro_stride_b = st_b;
+        ra.n_ro = hi - lo;
+        for (int j = 0; j < hi - lo; ++j) { ra.steps[j] = steps[lo + j]; li_kappa(p, steps[lo + j], &ra.kap[j]); }
+        void* kargs[] = {(void*)&ra};
+        e = hipLaunchKernel(kern, dim3(grid), dim3(256), kargs, lds, s);
+        if (e != hipSuccess) return fail(-3, "%s launch failed: %s", ksplit ? "k_li_heads_ksplit_ro" : "k_li_heads_mfma_ro", hipGetErrorString(e));
+        SNN_CHECK_LAUNCH(ksplit ? "k_li_heads_ksplit_ro" : "k_li_heads_mfma_ro");
+    }
+    return 0;
+}
+
+static int li_heads_readouts_impl(const uint32_t* spk, size_t spk_stride, const int* steps, int n, int M, int K, const float* w_heads_packed,
+                                  int NA, int NB, const snn_params* p, float* out_a, float* out_b, float* sum_a, float* sum_b,
+                                  bool half_split, snn_stream_t stream) {
+    if (half_split && !li_heads_reads_split(K, NA, NB)) return fail(-1, "snn_li_heads: split planes need the resident matrix-core kernel");
+    const int Kw = cdiv(K, 32), ldw = cdiv(NA + NB, 16) * 16;
+    const int force = p->precision == SNN_PRECISION_F32_STRICT ? 1 : knobs().li_heads;
+    const int step = force == 1 ? 256 : 64;
+    const unsigned long long st_a = (unsigned long long)M * NA, st_b = (unsigned long long)M * NB;
+    hipStream_t s = (hipStream_t)stream;
+    for (int col0 = 0; col0 < ldw; col0 += step) {
+        const int NOp = min(step, ldw - col0), nt = NOp / 16;
+        const int kind = li_heads_kind(Kw, NOp, force);
+        if (kind == 1) {                                       // the fp32 VALU kernel (f32_strict): one launch per readout
+            for (int j = 0; j < n; ++j) {
+                Kappa kap;
+                li_kappa(p, steps[j], &kap);
+                const int rc = li_heads_cols(spk, spk_stride, steps[j], M, Kw, w_heads_packed, NA, NB, kap, out_a + j * st_a, out_b + j * st_b,
+                                             sum_a ? sum_a + j * st_a : nullptr, sum_b ? sum_b + j * st_b : nullptr, half_split, force,
+                                             ldw, col0, NOp, s);
+                if (rc) return rc;
+            }
+            continue;
+        }
+        LiHeadsArgs a;
+        memset(&a, 0, sizeof(a));
+        a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
+        a.sum_a = sum_a; a.sum_b = sum_b; a.M = M; a.Kw = Kw; a.NOp = NOp; a.NA = NA; a.NB = NB; a.ldw = ldw; a.col0 = col0;
+        size_t lds;
+        if (kind == 3) {
+            lds = G3_LUT_BYTES + (size_t)4 * 2 * nt * 64 * 16;
+        } else {
+            a.n_groups = cdiv(M, 64);
+            a.half_split = half_split;
+            const size_t all = (size_t)Kw * 3 * NOp * 64;
+            a.resident = all <= 96 * 1024;
+            lds = G3_LUT_BYTES + (a.resident ? all : (size_t)2 * 3 * NOp * 64);
+        }
+        const bool ks = kind == 3;
+        const bool S = sum_a != nullptr;
+        int rc;
+        switch (nt) {
+            case 1: rc = S ? li_heads_ro_launch<1, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<1, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
+            case 2: rc = S ? li_heads_ro_launch<2, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<2, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
+            case 3: rc = S ? li_heads_ro_launch<3, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<3, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
+            default: rc = S ? li_heads_ro_launch<4, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<4, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int snn_li_heads_readouts(const uint32_t* spk, size_t spk_stride, const int* steps, int n_steps, int M, int K, const float* w_heads_packed,
+                          int NA, int NB, const snn_params* p, float* out_a, float* out_b, float* sum_a, float* sum_b, snn_stream_t s) {
+    if (check_steps(steps, n_steps, "snn_li_heads_readouts")) return -1;
+    if (!spk || !w_heads_packed || !p || !out_a || !out_b || M <= 0 || K <= 0 || NA <= 0 || NB <= 0)
+        return fail(-1, "snn_li_heads_readouts: bad argument");
+    if ((sum_a == nullptr) != (sum_b == nullptr)) return fail(-1, "snn_li_heads_readouts: sum_a and sum_b go together");
+    return li_heads_readouts_impl(spk, spk_stride, steps, n_steps, M, K, w_heads_packed, NA, NB, p, out_a, out_b, sum_a, sum_b, false, s);
 }
 
 // ---- whole heads ---------------------------------------------------------------------------------
@@ -1810,6 +1932,45 @@ int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, in
     return snn_rpn_head_forward_stages(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits,
                                        out_bbox, spike_counts, sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL,
                                        stream);
+}
+
+int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,
+                                  const snn_params* p, const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                                  float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
+                                  void* ws, size_t ws_bytes, snn_stream_t stream) {
+    if (check_steps(steps, n_steps, "snn_rpn_head_forward_readouts")) return -1;
+    if ((sum_logits == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_rpn_head_forward_readouts: sum_logits and sum_bbox go together");
+    const int T = steps[n_steps - 1];
+    // encoder + conv + LIF of the T pass (all its argument checks); the heads and counts then read the planes it left.  Spike-rate
+    // readouts run the conv as a spike-rate forward at T (same launch); its counts go to the first rows of spike_counts, zeroed below
+    int rc = snn_rpn_head_forward_stages(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, nullptr,
+                                         nullptr, ws, ws_bytes, SNN_STAGE_ENCODE | SNN_STAGE_CONV_LIF, stream);
+    if (rc) return rc;
+    int max_n = 0;
+    const long long P = rpn_positions(lv, n_levels, &max_n);
+    const int Cw = cdiv(C, 32);
+    const bool split = g_last_rpn_planes[1] != 0;
+    const uint32_t* spk = (const uint32_t*)((const char*)ws + g_last_rpn_planes[0]);
+    const size_t stride = (size_t)P * Cw;
+    rc = li_heads_readouts_impl(spk, stride, steps, n_steps, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox, sum_logits,
+                                sum_bbox, split, stream);
+    if (rc || !spike_counts) return rc;
+    // [n][n_levels][max_n]: popcounts of the shared LIF's planes t < T'_j per (level, image)
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * n_steps * n_levels * max_n, s) != hipSuccess)
+        return fail(-3, "hipMemsetAsync failed");
+    const StepList st = step_list(steps, n_steps);
+    long long pb = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int hw = lv[l].H * lv[l].W;
+        const int wpi = split ? hw * 4 : hw * Cw;                // blocks of four words [T][2][P][4]: the image's words of both halves
+        hipLaunchKernelGGL(k_count_spikes_ro, dim3(lv[l].N, max(1, min(256, wpi / 2048))), dim3(256), 0, s, spk + (size_t)pb * (split ? 4 : Cw),
+                           (unsigned long long)stride, split ? (unsigned long long)P * 4 : 0ull, wpi, st, spike_counts + (size_t)l * max_n,
+                           (unsigned long long)n_levels * max_n);
+        SNN_CHECK_LAUNCH("k_count_spikes_ro");
+        pb += (long long)lv[l].N * hw;
+    }
+    return 0;
 }
 
 // ---- finished spike-rate tensors -------------------------------------------------------------------
@@ -2085,10 +2246,30 @@ static bool det_b3_tiles(const snn_params* p, const DetWindows& w) {
 // ... which takes its encoder planes word-major [T][D/32][R] (and hands fc6's spikes to fc7 that way)
 static bool det_planes_wm(const snn_params* p, const DetWindows& w) { return det_b3_tiles(p, w) && knobs().planes != 1; }
 
+// a detector pass with any-time readouts (snn_det_head_forward_readouts): outputs [n][R][K] / [n][R][K4], counts [n][R]
+struct DetReadouts { const int* steps; int n; uint32_t *c6, *c7; };
+
+// the LI heads at the end of a detector pass: one readout at T (the plain forward), or the readout set with its spike counts
+static int det_heads_tail(const uint32_t* s6, const uint32_t* s7, int R, int Hd, int K, int K4, int T, const snn_params* p, const float* w_heads_packed,
+                          float* out_cls, float* out_bbox, float* sum_cls, float* sum_bbox, bool s6_wm, const DetReadouts* ro, snn_stream_t stream) {
+    const int Hw = cdiv(Hd, 32);
+    if (!ro) return snn_li_heads(s7, (size_t)R * Hw, T, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls, sum_bbox, stream);
+    int rc = li_heads_readouts_impl(s7, (size_t)R * Hw, ro->steps, ro->n, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls, sum_bbox,
+                                    false, stream);
+    if (rc || !ro->c6) return rc;
+    const StepList st = step_list(ro->steps, ro->n);
+    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, s6, (unsigned long long)R * Hw, R, Hw, s6_wm ? 1 : 0, st, ro->c6);
+    SNN_CHECK_LAUNCH("k_count_rows_ro");
+    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, s7, (unsigned long long)R * Hw, R, Hw, 0, st, ro->c7);
+    SNN_CHECK_LAUNCH("k_count_rows_ro");
+    return 0;
+}
+
 static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, const snn_params* p, const void* w6_packed,
                                 const void* w7_packed, const float* w_heads_packed, float* out_cls, float* out_bbox,
                                 uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws,
-                                bool enc_wm, const DetWindows& win, bool enc_periods, snn_stream_t stream, int k_inner = 0, bool folded = false) {
+                                bool enc_wm, const DetWindows& win, bool enc_periods, snn_stream_t stream, int k_inner = 0, bool folded = false,
+                                const DetReadouts* ro = nullptr) {
     // folded (round 5): the encoder launch already wrote the planes in fc6's permuted order, e_3 .. compressed (k_encode_rows_perm): no
     // k_permute_planes, no k_compress_planes - fc6 must then run the structured-sparse launch (it was asked beforehand)
     size_t o_enc, o_cur, o_s6, o_s7, need;
@@ -2126,8 +2307,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
         if (!mx_tile_ok(win.fc6.n) || !mx_tile_ok(win.fc7.n)) return fail(-4, "snn_det_head_forward: T=%d does not fit a 512-row tile of the mxfp6 kernels", T);
         if ((rc = spike_gemm_lif_mx_impl(enc, T, R, D, Hd, p, (const uint32_t*)w6_packed, s6, (size_t)R * Hw, spk6_count, stream, &win.fc6))) return rc;
         if ((rc = spike_gemm_lif_mx_impl(s6, T, R, Hd, Hd, p, (const uint32_t*)w7_packed, s7, (size_t)R * Hw, spk7_count, stream, &win.fc7))) return rc;
-        return snn_li_heads(s7, (size_t)R * Hw, T, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls,
-                            sum_bbox, stream);
+        return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, false, ro, stream);
     }
     if ((enc_wm || enc_periods) && !det_b3_tiles(p, win)) return fail(-1, "snn_det_head_forward: word-major / period planes without the fused bf16x3 layers");
     if (det_b3_tiles(p, win)) {
@@ -2149,8 +2329,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
         g_last_fc_sparse = rc;
         if (rc == 0 && (rc = launch_gemm3(G3_FC_LIF_TILE, t6.mt, wn, a6, s))) return rc;
         if ((rc = launch_gemm3(G3_FC_LIF_TILE, t7.mt, wn, a7, s))) return rc;
-        return snn_li_heads(s7, (size_t)R * Hw, T, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls,
-                            sum_bbox, stream);
+        return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, enc_wm, ro, stream);
     }
     // fc6 for all (live) time steps at once: rows m = (t - t0)*R + r   (faster_rcnn.py:498)
     const uint32_t* a6 = enc + (size_t)win.fc6.t0 * R * cdiv(D, 32);
@@ -2163,8 +2342,8 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
             : snn_spike_gemm(a7, win.fc7.n * R, Hd, Hd, (const float*)w7_packed, cur, Hp, stream);                       // :500
     if (rc) return rc;
     if ((rc = lif_scan_window(cur, T, win.fc7, R, Hd, Hp, p, s7, (size_t)R * Hw, spk7_count, stream))) return rc;   // :501
-    return snn_li_heads(s7, (size_t)R * Hw, T, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls,
-                        sum_bbox, stream);                                                               // :505-510
+    return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, false, ro,
+                          stream);                                                                       // :505-510
 }
 
 int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
@@ -2175,10 +2354,37 @@ int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, in
                                   sum_cls, sum_bbox, ws, ws_bytes, stream);
 }
 
+static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream, const DetReadouts* ro);
+
 int snn_det_head_forward_k(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
                            const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                            float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                            float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+}
+
+int snn_det_head_forward_readouts(const float* x, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps, const snn_params* p,
+                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                  float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    if (check_steps(steps, n_steps, "snn_det_head_forward_readouts")) return -1;
+    if ((spk6_count == nullptr) != (spk7_count == nullptr)) return fail(-1, "snn_det_head_forward_readouts: spk6_count and spk7_count go together");
+    if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_det_head_forward_readouts: sum_cls and sum_bbox go together");
+    // spike-rate readouts: the pass runs as a spike-rate forward at T (same launches, windows of every lif6 step); its per-RoI counts land in
+    // the first rows of the count buffers, which the readout counts then overwrite in stream order
+    const DetReadouts ro{steps, n_steps, spk6_count, spk7_count};
+    return det_head_forward_impl(x, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
+                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, &ro);
+}
+
+static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream, const DetReadouts* ro) {
     if (!x || !p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
         return fail(-1, "snn_det_head_forward: null argument");
     if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward: bad shape");
@@ -2230,7 +2436,7 @@ int snn_det_head_forward_k(const float* x, int R, int D, int Hd, int K, int K4, 
         if ((rc = encode_rows_impl(x, R, D, win.enc_steps, p, enc_dst, (size_t)R * cdiv(D, 32), wm, stream, per))) return rc;
     }
     return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold);
+                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold, ro);
 }
 
 int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
@@ -2243,12 +2449,46 @@ int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels
                                            w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
 }
 
+static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                          snn_stream_t stream, const DetReadouts* ro);
+
 int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
                                     const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
                                     const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
                                     const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                     uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                     snn_stream_t stream) {
+    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
+                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
+                                          ws_bytes, stream, nullptr);
+}
+
+int snn_det_head_forward_roialign_readouts(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+                                           const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, const int* steps,
+                                           int n_steps, const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                           const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                           uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                           snn_stream_t stream) {
+    if (check_steps(steps, n_steps, "snn_det_head_forward_roialign_readouts")) return -1;
+    if ((spk6_count == nullptr) != (spk7_count == nullptr))
+        return fail(-1, "snn_det_head_forward_roialign_readouts: spk6_count and spk7_count go together");
+    if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_det_head_forward_roialign_readouts: sum_cls and sum_bbox go together");
+    const DetReadouts ro{steps, n_steps, spk6_count, spk7_count};     // (as snn_det_head_forward_readouts)
+    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
+                                          w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
+                                          ws_bytes, stream, &ro);
+}
+
+static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                          snn_stream_t stream, const DetReadouts* ro) {
     if (!p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
         return fail(-1, "snn_det_head_forward_roialign: null argument");
     if (R <= 0 || C <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward_roialign: bad shape");
@@ -2306,7 +2546,7 @@ int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_leve
         if (rc) return rc;
     }
     return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold);
+                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold, ro);
 }
 
 int snn_det_exchange_payload(const float* class_logits, const float* box_regression, int N, int rois_per_image, int K,

@@ -136,6 +136,49 @@ class FastRCNNPredictorSNNFull(nn.Module):
                                             self._params(prec), w6, w7, wh, spike_rates=self.spike_rates, w6_inner=self.fc6_inner(prec))
         return self._finish(out, rois.shape[0], rois.device)
 
+    @torch.no_grad()
+    def forward_readouts(self, x, steps) -> dict:
+        """Every T' of ``steps`` from ONE head pass at T = steps[-1]: {T': (class_logits, box_regression)}, or {T': rates} with
+        ``spike_rates`` - each what ``forward`` returns for num_steps = T'.  ``num_steps`` is not touched."""
+        steps = ops.check_steps(steps)
+        Hd, K = self.representation_size, self.num_classes
+        K4 = self.bbox_pred.weight.shape[0]
+        prec = self._resolve_precision()
+        w6, w7, wh = self._packed(prec)
+        x = x.flatten(start_dim=1)
+        if x.shape[1] != self.in_channels:
+            raise ValueError("expected %d input features, got %d" % (self.in_channels, x.shape[1]))
+        out = ops.det_head_forward_readouts(x, Hd, K, K4, steps, self._params(prec), w6, w7, wh, spike_rates=self.spike_rates,
+                                            w6_inner=self.fc6_inner(prec))
+        return self._finish_readouts(out, steps)
+
+    @torch.no_grad()
+    def forward_roialign_readouts(self, feats, scales, rois, roi_level, steps) -> dict:
+        """forward_roialign with a readout per T' of ``steps`` (see forward_readouts)"""
+        steps = ops.check_steps(steps)
+        Hd, K = self.representation_size, self.num_classes
+        K4 = self.bbox_pred.weight.shape[0]
+        prec = self._resolve_precision()
+        w6, w7, wh = self._packed(prec)
+        if feats[0].shape[1] * 49 != self.in_channels:
+            raise ValueError("expected %d input features, got %d x 49" % (self.in_channels, feats[0].shape[1]))
+        out = ops.det_head_forward_roialign_readouts(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, Hd, K, K4, steps,
+                                                     self._params(prec), w6, w7, wh, spike_rates=self.spike_rates,
+                                                     w6_inner=self.fc6_inner(prec))
+        return self._finish_readouts(out, steps)
+
+    def _finish_readouts(self, out, steps):
+        cls, bbox, (c6, c7, s_c, s_b) = out
+        res = {}
+        for j, T in enumerate(steps):
+            if not self.spike_rates:
+                res[T] = (cls[j], bbox[j])
+                continue
+            rates = ops.det_rates((c6[j], c7[j], s_c[j], s_b[j]), self.in_channels, self.representation_size, self.num_classes,
+                                  self.bbox_pred.weight.shape[0], T, self.only_one_bbox)
+            res[T] = [rates[0], rates[1], rates[2], rates[3]]
+        return res
+
     def _finish(self, out, R, dev):
         cls, bbox, extras = out
         if not self.spike_rates:

@@ -35,12 +35,16 @@ class GeneralizedRCNN(nn.Module):
             return list(rpn_rates) + list(det_rates)
         proposals, proposal_extras = self.rpn(images, features, targets)            # :114
         detections, _ = self.roi_heads(features, proposals, images.image_sizes, targets)   # :118
-        detections = self.transform.postprocess(detections, images.image_sizes, original_image_sizes)
+        return self.finish_detections(detections, proposal_extras, images.image_sizes, original_image_sizes)
+
+    def finish_detections(self, detections, proposal_extras, image_sizes, original_image_sizes):
+        """the end of ``forward`` (generalized_rcnn.py:119-132): back to the original sizes, the RPN's extras merged in"""
+        detections = self.transform.postprocess(detections, image_sizes, original_image_sizes)
         for i in range(len(detections)):                                            # :125-129
             for k, v in proposal_extras[i].items():
                 detections[i][k] = v
         if detections and "all_boxes" in detections[0]:
-            detections = self.postprocess(detections, images.image_sizes, original_image_sizes)
+            detections = self.postprocess(detections, image_sizes, original_image_sizes)
         return detections
 
     def postprocess(self, result: List[Dict[str, Tensor]], image_shapes: List[Tuple[int, int]],

@@ -2,6 +2,7 @@
 memory, the current HIP stream, nothing else.  Every function raises if the input is not a CUDA/HIP
 tensor — there is no CPU or eager fallback."""
 import ctypes as C
+import numbers
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -610,6 +611,150 @@ def det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, Hd: int
                                                    _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_roialign")
     return out_cls, out_bbox, (c6, c7, s_c, s_b)
 
+
+
+# ---------------------------------------------------------------------------------------------
+# any-time readouts: every T' of a time-step sweep from one head pass (include/snn_hip.h)
+# ---------------------------------------------------------------------------------------------
+def check_steps(steps) -> Tuple[int, ...]:
+    """a readout set: ints, strictly increasing, each in 1 .. SNN_MAX_STEPS (ValueError otherwise; nothing touches a device)"""
+    if isinstance(steps, (str, bytes)) or not hasattr(steps, "__iter__"):
+        raise ValueError("steps must be a sequence of ints, got %r" % (steps,))
+    steps = tuple(steps)
+    if not 1 <= len(steps) <= _lib.SNN_MAX_STEPS:
+        raise ValueError("steps: %d readouts (1 .. %d)" % (len(steps), _lib.SNN_MAX_STEPS))
+    for j, t in enumerate(steps):
+        if isinstance(t, bool) or not isinstance(t, numbers.Integral):
+            raise ValueError("steps[%d] = %r is not an int" % (j, t))
+        if not 1 <= int(t) <= _lib.SNN_MAX_STEPS:
+            raise ValueError("steps[%d] = %d outside [1, %d]" % (j, t, _lib.SNN_MAX_STEPS))
+        if j and int(t) <= int(steps[j - 1]):
+            raise ValueError("steps must be strictly increasing (%d after %d)" % (t, steps[j - 1]))
+    return tuple(int(t) for t in steps)
+
+
+def _steps_arg(steps):
+    arr = (C.c_int * len(steps))(*steps)
+    return arr, len(steps)
+
+
+def li_heads_readouts(spk: torch.Tensor, K: int, w_heads_packed: torch.Tensor, NA: int, NB: int, p: snn_params, steps,
+                      want_sums: bool = False):
+    """snn_li_heads_readouts on planes [T, M, Kw] (T >= steps[-1]): outputs [n, M, NA] / [n, M, NB] (+ sums)"""
+    steps = check_steps(steps)
+    _need_gpu(spk, "spike planes")
+    lib = _lib.load()
+    T, M, Kw = spk.shape
+    dev, n = spk.device, len(steps)
+    out_a = torch.empty((n, M, NA), dtype=torch.float32, device=dev)
+    out_b = torch.empty((n, M, NB), dtype=torch.float32, device=dev)
+    sum_a = torch.empty_like(out_a) if want_sums else None
+    sum_b = torch.empty_like(out_b) if want_sums else None
+    st, ns = _steps_arg(steps)
+    _lib.check(lib.snn_li_heads_readouts(_ptr(spk), M * Kw, st, ns, M, K, _ptr(w_heads_packed), NA, NB, C.byref(p), _ptr(out_a),
+                                         _ptr(out_b), _ptr(sum_a), _ptr(sum_b), _stream()), "snn_li_heads_readouts")
+    return (out_a, out_b, sum_a, sum_b) if want_sums else (out_a, out_b)
+
+
+def rpn_head_forward_readouts(feats: Sequence[torch.Tensor], C_: int, A: int, steps, p: snn_params,
+                              w_shared_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False):
+    """one RPN head pass at T = steps[-1] with a readout per T' in steps: (out_logits [n,P,A], out_bbox [n,P,4A], level_rows,
+    (counts [n,levels,max_n], sum_l, sum_b, rates: list of [levels,3,max_n,2] per readout))"""
+    steps = check_steps(steps)
+    lib = _lib.load()
+    if len(feats) == 0 or len(feats) > _lib.SNN_MAX_LEVELS:
+        raise _lib.SnnHipError("RPN head takes 1..%d feature levels, got %d" % (_lib.SNN_MAX_LEVELS, len(feats)))
+    feats = [_f32c(f) for f in feats]
+    for f in feats:
+        _need_gpu(f, "feature map")
+        if f.dim() != 4 or f.shape[1] != C_:
+            raise _lib.SnnHipError("feature map must be [N,%d,H,W], got %s" % (C_, tuple(f.shape)))
+    dev, n = feats[0].device, len(steps)
+    lv = (snn_rpn_level * len(feats))()
+    rows = []
+    for l, f in enumerate(feats):
+        lv[l] = snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0)
+        rows.append(f.shape[0] * f.shape[2] * f.shape[3])
+    P, max_n = sum(rows), max(f.shape[0] for f in feats)
+    ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, steps[-1], p.precision))
+    out_l = torch.empty((n, P, A), dtype=torch.float32, device=dev)
+    out_b = torch.empty((n, P, 4 * A), dtype=torch.float32, device=dev)
+    counts = sum_l = sum_b = None
+    if spike_rates:
+        counts = torch.empty((n, len(feats), max_n), dtype=torch.int64, device=dev)
+        sum_l, sum_b = torch.empty_like(out_l), torch.empty_like(out_b)
+    st, ns = _steps_arg(steps)
+    _lib.check(lib.snn_rpn_head_forward_readouts(lv, len(feats), C_, A, st, ns, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed),
+                                                 _ptr(out_l), _ptr(out_b), _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(),
+                                                 _stream()), "snn_rpn_head_forward_readouts")
+    rates = None
+    if spike_rates:
+        rates = []
+        rws = _WS_RATES.get(dev, lib.snn_rpn_rates_workspace_bytes(len(feats), max_n))
+        for j, T in enumerate(steps):
+            r = torch.empty((len(feats), 3, max_n, 2), dtype=torch.float32, device=dev)
+            _lib.check(lib.snn_rpn_rates(lv, len(feats), C_, A, T, _ptr(counts[j]), _ptr(sum_l[j]), _ptr(sum_b[j]), _ptr(r), _ptr(rws),
+                                         rws.numel(), _stream()), "snn_rpn_rates")
+            rates.append(r)
+    return out_l, out_b, rows, (counts, sum_l, sum_b, rates)
+
+
+def _det_readout_outputs(R, K, K4, n, spike_rates, dev):
+    out_cls = torch.empty((n, R, K), dtype=torch.float32, device=dev)
+    out_bbox = torch.empty((n, R, K4), dtype=torch.float32, device=dev)
+    c6 = c7 = s_c = s_b = None
+    if spike_rates:
+        c6 = torch.empty((n, R), dtype=torch.int32, device=dev)
+        c7 = torch.empty((n, R), dtype=torch.int32, device=dev)
+        s_c, s_b = torch.empty_like(out_cls), torch.empty_like(out_bbox)
+    return out_cls, out_bbox, (c6, c7, s_c, s_b)
+
+
+def det_head_forward_readouts(x: torch.Tensor, Hd: int, K: int, K4: int, steps, p: snn_params, w6_packed: torch.Tensor,
+                              w7_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False, w6_inner: int = 0):
+    """one detector head pass at T = steps[-1]: (out_cls [n,R,K], out_bbox [n,R,K4], (c6 [n,R], c7, sum_cls, sum_bbox))"""
+    steps = check_steps(steps)
+    lib = _lib.load()
+    _need_gpu(x, "box features")
+    x = _f32c(x).flatten(1)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    R, D = x.shape
+    out_cls, out_bbox, extras = _det_readout_outputs(R, K, K4, len(steps), spike_rates, x.device)
+    if R == 0:
+        return out_cls, out_bbox, extras
+    ws = _WS.get(x.device, lib.snn_det_head_workspace_bytes(R, D, Hd, K, K4, steps[-1], p.precision))
+    c6, c7, s_c, s_b = extras
+    st, ns = _steps_arg(steps)
+    _lib.check(lib.snn_det_head_forward_readouts(_ptr(x), R, D, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
+                                                 _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7), _ptr(s_c), _ptr(s_b),
+                                                 _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_readouts")
+    return out_cls, out_bbox, extras
+
+
+def det_head_forward_roialign_readouts(feats, scales, rois, roi_batch, roi_level, Hd: int, K: int, K4: int, steps, p: snn_params,
+                                       w6_packed, w7_packed, w_heads_packed, spike_rates: bool = False, w6_inner: int = 0):
+    """det_head_forward_readouts fed straight from the FPN maps (RoIAlign fused with the encoder)"""
+    steps = check_steps(steps)
+    lib = _lib.load()
+    lv, keep = _roi_levels(feats, scales)
+    Cc = keep[0].shape[1]
+    rois = _f32c(rois)
+    roi_batch = roi_batch.to(torch.int32).contiguous()
+    roi_level = roi_level.to(torch.int32).contiguous()
+    R = rois.shape[0]
+    out_cls, out_bbox, extras = _det_readout_outputs(R, K, K4, len(steps), spike_rates, rois.device)
+    if R == 0:
+        return out_cls, out_bbox, extras
+    ws = _WS.get(rois.device, lib.snn_det_head_workspace_bytes(R, Cc * 49, Hd, K, K4, steps[-1], p.precision))
+    c6, c7, s_c, s_b = extras
+    st, ns = _steps_arg(steps)
+    _lib.check(lib.snn_det_head_forward_roialign_readouts(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4,
+                                                          st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
+                                                          _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7),
+                                                          _ptr(s_c), _ptr(s_b), _ptr(ws), ws.numel(), _stream()),
+               "snn_det_head_forward_roialign_readouts")
+    return out_cls, out_bbox, extras
 
 # ---------------------------------------------------------------------------------------------
 # greedy / batched NMS (glue on either side of the heads)

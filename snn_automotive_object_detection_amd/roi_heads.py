@@ -138,6 +138,20 @@ class RoIHeadsSNN(nn.Module):
         else:
             box_features = pool(features, proposals, image_shapes)                   # roi_heads.py:1217
             head_out = head(box_features)                                            # roi_heads.py:1230 (HIP)
+        return self.detections_from_head(head_out, proposals, image_shapes)
+
+    def head_readouts(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]], steps) -> dict:
+        """the head call of ``forward`` with a readout per T_det of ``steps`` (one pass at steps[-1]; the fused RoIAlign path where
+        ``forward`` takes it): {T_det: head output}"""
+        pool, head = self.box_roi_pool, self.box_head_and_predictor
+        if (self.fuse_roi_align and hasattr(head, "forward_roialign_readouts") and hasattr(pool, "assign")
+                and tuple(pool.output_size) == (7, 7) and pool.sampling_ratio == 2):
+            feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
+            return head.forward_roialign_readouts(feats, scales, rois, lvl, steps)
+        return head.forward_readouts(pool(features, proposals, image_shapes), steps)
+
+    def detections_from_head(self, head_out, proposals: List[Tensor], image_shapes: List[Tuple[int, int]]):
+        """the part of ``forward`` after the head call: detections (or, in spike-rate mode, the head's rates)"""
         if getattr(self.box_head_and_predictor, "spike_rates", False):
             return head_out                                                          # roi_heads.py:1219-1223
         class_logits, box_regression = head_out

@@ -168,6 +168,34 @@ class RPNHeadSNN(nn.Module):
         return logits, bbox_reg
 
 
+    @torch.no_grad()
+    def forward_readouts(self, x: List[Tensor], steps) -> dict:
+        """Every T' of ``steps`` (strictly increasing ints in 1 .. 32) from ONE head pass at T = steps[-1]:
+        {T': (logits, bbox_reg)} - with ``spike_rates``, {T': (logits, bbox_reg, rates)} - each what ``forward`` returns for
+        num_steps = T' (include/snn_hip.h: snn_rpn_head_forward_readouts states what is bit-exact).  ``num_steps`` is not touched."""
+        steps = ops.check_steps(steps)
+        C, A = self.in_channels, self.num_anchors
+        prec = self._resolve_precision()
+        w_shared = self._packed_shared(prec)
+        w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
+        out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward_readouts(
+            list(x), C, A, steps, self._params(prec), w_shared, w_heads, spike_rates=self.spike_rates)
+        res = {}
+        for j, T in enumerate(steps):
+            logits, bbox_reg, rates = [], [], []
+            pos = 0
+            for l, f in enumerate(x):
+                N, H, W = f.shape[0], f.shape[2], f.shape[3]
+                n = rows[l]
+                logits.append(out_l[j, pos:pos + n].view(N, H, W, A).permute(0, 3, 1, 2))
+                bbox_reg.append(out_b[j, pos:pos + n].view(N, H, W, 4 * A).permute(0, 3, 1, 2))
+                if self.spike_rates:
+                    rates += [rate_rows[j][l, k, :N] for k in range(3)]
+                pos += n
+            res[T] = (logits, bbox_reg, rates) if self.spike_rates else (logits, bbox_reg)
+        return res
+
+
 # ---------------------------------------------------------------------------------------------
 # Stock-torch caller of the head (inference side of /root/reference/rpn.py:299-703).  Not part of
 # the accelerated path; present so that the detector runs end-to-end without torchvision.
@@ -341,6 +369,11 @@ class RegionProposalNetwork(nn.Module):
             raise NotImplementedError("inference only: training the RPN is out of scope (DESIGN.md §7)")
         feats = list(features.values())
         head_out = self.head(feats)                                                   # rpn.py:613 (608-610 in spike-rate mode)
+        return self.proposals_from_head(images, feats, head_out)
+
+    def proposals_from_head(self, images, feats, head_out):
+        """the part of ``forward`` after the head call (rpn.py:614-701): proposals from the head's outputs; also the per-T_rpn
+        step of sweep.timestep_sweep"""
         objectness, pred_bbox_deltas = head_out[:2]
         # spike-rate mode: the head's third value takes the place of `losses` (rpn.py:698-701, "losses = spike_rates")
         rates = head_out[2] if len(head_out) == 3 else None
