@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the spiking-heads hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (defaults: 1, 100, 10)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]          (defaults: 1, 100, 10)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the headline line.  --full adds
+everything else the benchmark measures and checks: the per-kernel breakdown, roofline and held clock of the headline, the
+exchange by itself (N > 1), the CPU baselines and the legs outside the headline timing (`extra`); the --no-* options trim it.
+--sweep-t runs its grid whenever it is given.
 
 N > 1 works both ways: under torchrun (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
 --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment, /root/reference/utils.py:268-312's
@@ -20,13 +25,13 @@ Inputs (`--inputs backbone`, default): the pyramid is the FPN output of the (ran
 `torch.rand(3,1024,2048)` images through the reference's transform, the RoI features are the
 7x7 RoIAlign of 1000 seeded boxes per image on that pyramid.  `--inputs randn`: N(0,1) tensors (round-1 behaviour).
 
-Prints ONE JSON line (rank 0): metric images/s + "roofline" (dominant kernel, timed live with HIP events
+Prints ONE JSON line (rank 0): metric images/s; with --full also "roofline" (dominant kernel, timed live with HIP events
 on the launch stream, on this workload's own encoder planes) + "cpu_baseline" (the oracle on the host cores, bounded sample,
 rank 0 at N=1 only) + "extra" (outside the headline timing, N=1 only): a sustained >= 2 s window of the same step, the
 end-to-end model (BASELINE config[2]), the BDD per-rank share (config[3]) and the T=16/24 spike-rate stress workload
 (config[4]), each with the launch time and roofline fraction of its own conv+LIF kernel.
 
-N > 1 also runs BASELINE.json's config[3] for real as the `dp_e2e` leg: every rank builds create_model("bdd", 11), takes its
+N > 1 with --full also runs BASELINE.json's config[3] for real as the `dp_e2e` leg: every rank builds create_model("bdd", 11), takes its
 contiguous shard of 4 x N seeded rand(3,720,1280) images (4 per GPU; train.py:598-601), runs the WHOLE model and the ranks
 all-gather the decoded detections (dp.all_gather_detections: the RCCL counterpart of coco_eval.py:158-177).
 
@@ -742,6 +747,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)      # (0.27 s of timed work: the fence around a 20-step window was 1.5 % of it, profiles/r5_warmup_steps.txt)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else: per-kernel breakdown, roofline and held clock, the exchange by itself (N > 1), "
+                         "CPU baselines and the legs outside the headline timing; the --no-* options below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the legs outside the headline timing (sustained / e2e / bdd / stress / alt precision)")
     ap.add_argument("--no-alt", action="store_true", help="skip the extra timing leg with the other precision")
@@ -756,7 +764,8 @@ def main():
     ap.add_argument("--detector-snn", action="store_true", help="accepted for CLI compatibility (always on)")
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--sustain-s", type=float, default=2.0)
-    ap.add_argument("--sweep-t", action="store_true", help="only the throughput-vs-T grid (T_rpn 4..12, T_det 8..16) besides the headline")
+    ap.add_argument("--sweep-t", action="store_true", help="the throughput-vs-T grid (T_rpn 4..12, T_det 8..16) besides the headline "
+                                                                 "(with --full: instead of the legs outside the headline timing)")
     ap.add_argument("--no-dp-e2e", action="store_true", help="skip the whole-model data-parallel leg (config[3])")
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the held-clock probe (runs under rocprofv3 --pmc, where kernels are serialised and the probe says nothing)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -828,51 +837,8 @@ def main():
     ms = dt / args.steps * 1e3
     value = world * wl["batch"] * args.steps / dt
 
-    # ---- the exchange step by itself (outside the headline timing) ----
-    exchange = {"backend": dp.backend_name(), "ranks": world, "ms": None}
-    if world > 1:
-        payload, counts = leg.exchange_only()
-        fence()
-        xs = []
-        for _ in range(max(5, args.warmup)):
-            fence()
-            t0 = time.perf_counter()
-            g_payload, g_counts = dp.all_gather_detection_tensors(payload, counts)
-            torch.cuda.synchronize()
-            xs.append((time.perf_counter() - t0) * 1e3)
-        exchange.update(ms=round(statistics.median(xs), 4), ranks=dist.get_world_size(),
-                        rows_gathered=int(g_payload.shape[0]), payload_bytes_per_rank=int(payload.numel() * 4 + counts.numel() * 4))
-        assert g_payload.shape[0] == world * wl["batch"] and int(g_counts.min()) >= 0
-
-    iters = max(3, min(args.steps, 10))
-    bd = leg.kernel_breakdown(iters)
-    conv_fl, rpn_fl, det_fl = algorithmic_flops(wl)
-    # HBM bytes per launch of the dominant kernel: NOT measured by this run (PMC counters need rocprofv3 around the process) but
-    # read from the committed PMC passes of the same launch (separate --pmc FETCH_SIZE / WRITE_SIZE runs, tools/prof_round.sh ->
-    # tools/make_traffic_json.py), per workload
     from snn_automotive_object_detection_amd import build as _build
     source_digest = _build.source_digest()                       # content hash of everything libsnnhip.so is built from
-    TRAFFIC_JSON = "r6_traffic.json"
-
-    def committed_traffic(workload):
-        if args.t_rpn or dead_steps_kept():
-            return None, None, {}
-        return load_committed_traffic(os.path.join(ROOT, "profiles", TRAFFIC_JSON), source_digest, workload, args.precision)
-    traffic, traffic_source, traffic_prof = committed_traffic(args.workload)
-
-    def roofline_of(l, bd_, step_ms, t_, t_src, t_prof):
-        """roofline of a leg + the clock the chip held under it: `frac` prices the launch against the peaks at the NOMINAL 2.4 GHz; boxes of this
-        pool hold different clocks under the same matrix-core load (MI355X_MICROARCH.md 'DVFS give-back' item 5), so `frac_at_held_clock` =
-        frac x 2.4 / held clock is the part of the fraction that is the kernel's and not the box's"""
-        rf = {**l.roofline(bd_["rpn_conv3x3_lif"], t_, t_src), **t_prof}
-        clk = l.held_clocks(step_ms, bd_["rpn_conv3x3_lif"]) if not args.no_clock_probe else {"step_ghz": None, "conv_lif_ghz": None, "note": "--no-clock-probe"}
-        if clk.get("conv_lif_ghz"):
-            rf["held_clock_ghz"] = clk["conv_lif_ghz"]
-            rf["frac_at_held_clock"] = round(rf["frac"] * NOMINAL_CLOCK_GHZ / clk["conv_lif_ghz"], 4)
-            rf["launch_cycles_at_held_clock"] = round(bd_["rpn_conv3x3_lif"] * 1e-3 * clk["conv_lif_ghz"] * 1e9)
-        return rf, clk
-    roofline, held = roofline_of(leg, bd, ms, traffic, traffic_source, traffic_prof)
-
     out = {
         "metric": "images/sec (T_rpn=%d,T_det=%d, %dx%d b=%d) spiking RPN+RoI heads forward" % (
             wl["T_rpn"], wl["T_det"], wl["image"][0], wl["image"][1], wl["batch"]),
@@ -888,29 +854,71 @@ def main():
                                    wl["levels"][-1][1], wl["T_det"], wl["batch"] * ROIS_PER_IMG, wl["K"], leg.input_note),
                    "global_batch": wl["batch"] * world, "parallelism": "dp%d" % world,
                    "exchange": ("all-gather of per-image detections [100x6] (%s, %d ranks)" % (
-                       "RCCL" if exchange["backend"] == "nccl" else exchange["backend"], exchange["ranks"])) if world > 1 else "none"},
-        "roofline": roofline,
-        "held_clock": held,
+                       "RCCL" if dp.backend_name() == "nccl" else dp.backend_name(), world)) if world > 1 else "none"},
         "build": {"source_digest": source_digest, "lib": os.path.relpath(_build.LIB_PATH, ROOT) if not os.environ.get("SNN_HIP_LIB") else os.environ["SNN_HIP_LIB"]},
-        "breakdown_ms": {k: round(v, 3) for k, v in bd.items()},
-        "heads_tflops": round((rpn_fl + det_fl) / ((bd["rpn_head"] + bd["det_head"]) * 1e-3) / 1e12, 2),
-        "exchange": exchange,
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
-    enc_rpn = out["roofline"].get("encoders", {}).get("rpn")
-    if enc_rpn and enc_rpn.get("algorithmic_hbm_bytes") and bd["rpn_encode"] > 0:      # (the RPN encoder is also timed live: stage 1 of the head by itself)
-        enc_rpn["live_ms"] = round(bd["rpn_encode"], 4)
-        enc_rpn["live_gb_per_s"] = round(enc_rpn["algorithmic_hbm_bytes"] / (bd["rpn_encode"] * 1e-3) / 1e9, 1)
     if "SNN_DP_DEVICE" in os.environ and world > 1:
         out["config"]["oversubscribed"] = "%d ranks on device %s (test of the N-rank path, not a scaling measurement)" % (world, os.environ["SNN_DP_DEVICE"])
 
-    # ---- the CPU baseline of the headline (the oracle on the host cores, same tensors): before the side legs, whose own single passes then find the
-    # thread pool and the allocator warm
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(leg, args.cpu_repeats)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    # ---- what the headline does not need runs with --full only (and --sweep-t's grid, asked for by name) ----
+    if args.full:
+        # the exchange step by itself (outside the headline timing)
+        exchange = {"backend": dp.backend_name(), "ranks": world, "ms": None}
+        if world > 1:
+            payload, counts = leg.exchange_only()
+            fence()
+            xs = []
+            for _ in range(max(5, args.warmup)):
+                fence()
+                t0 = time.perf_counter()
+                g_payload, g_counts = dp.all_gather_detection_tensors(payload, counts)
+                torch.cuda.synchronize()
+                xs.append((time.perf_counter() - t0) * 1e3)
+            exchange.update(ms=round(statistics.median(xs), 4), ranks=dist.get_world_size(),
+                            rows_gathered=int(g_payload.shape[0]), payload_bytes_per_rank=int(payload.numel() * 4 + counts.numel() * 4))
+            assert g_payload.shape[0] == world * wl["batch"] and int(g_counts.min()) >= 0
+
+        iters = max(3, min(args.steps, 10))
+        bd = leg.kernel_breakdown(iters)
+        conv_fl, rpn_fl, det_fl = algorithmic_flops(wl)
+        # HBM bytes per launch of the dominant kernel: NOT measured by this run (PMC counters need rocprofv3 around the process) but
+        # read from the committed PMC passes of the same launch (separate --pmc FETCH_SIZE / WRITE_SIZE runs, tools/prof_round.sh ->
+        # tools/make_traffic_json.py), per workload
+        TRAFFIC_JSON = "r6_traffic.json"
+
+        def committed_traffic(workload):
+            if args.t_rpn or dead_steps_kept():
+                return None, None, {}
+            return load_committed_traffic(os.path.join(ROOT, "profiles", TRAFFIC_JSON), source_digest, workload, args.precision)
+        traffic, traffic_source, traffic_prof = committed_traffic(args.workload)
+
+        def roofline_of(l, bd_, step_ms, t_, t_src, t_prof):
+            """roofline of a leg + the clock the chip held under it: `frac` prices the launch against the peaks at the NOMINAL 2.4 GHz; boxes of this
+            pool hold different clocks under the same matrix-core load (MI355X_MICROARCH.md 'DVFS give-back' item 5), so `frac_at_held_clock` =
+            frac x 2.4 / held clock is the part of the fraction that is the kernel's and not the box's"""
+            rf = {**l.roofline(bd_["rpn_conv3x3_lif"], t_, t_src), **t_prof}
+            clk = l.held_clocks(step_ms, bd_["rpn_conv3x3_lif"]) if not args.no_clock_probe else {"step_ghz": None, "conv_lif_ghz": None, "note": "--no-clock-probe"}
+            if clk.get("conv_lif_ghz"):
+                rf["held_clock_ghz"] = clk["conv_lif_ghz"]
+                rf["frac_at_held_clock"] = round(rf["frac"] * NOMINAL_CLOCK_GHZ / clk["conv_lif_ghz"], 4)
+                rf["launch_cycles_at_held_clock"] = round(bd_["rpn_conv3x3_lif"] * 1e-3 * clk["conv_lif_ghz"] * 1e9)
+            return rf, clk
+        roofline, held = roofline_of(leg, bd, ms, traffic, traffic_source, traffic_prof)
+        out.update(roofline=roofline, held_clock=held, breakdown_ms={k: round(v, 3) for k, v in bd.items()},
+                   heads_tflops=round((rpn_fl + det_fl) / ((bd["rpn_head"] + bd["det_head"]) * 1e-3) / 1e12, 2), exchange=exchange)
+        enc_rpn = out["roofline"].get("encoders", {}).get("rpn")
+        if enc_rpn and enc_rpn.get("algorithmic_hbm_bytes") and bd["rpn_encode"] > 0:      # (the RPN encoder is also timed live: stage 1 of the head by itself)
+            enc_rpn["live_ms"] = round(bd["rpn_encode"], 4)
+            enc_rpn["live_gb_per_s"] = round(enc_rpn["algorithmic_hbm_bytes"] / (bd["rpn_encode"] * 1e-3) / 1e9, 1)
+
+        # the CPU baseline of the headline (the oracle on the host cores, same tensors): before the side legs, whose own single passes then find the
+        # thread pool and the allocator warm
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(leg, args.cpu_repeats)
+        elif rank == 0:
+            out["cpu_baseline"] = None
 
     extra = {}
 
@@ -921,7 +929,7 @@ def main():
             extra[name] = {"error": repr(e)[:500]}
             print("bench.py: side leg %r failed on rank %d: %r" % (name, rank, e), file=sys.stderr)
 
-    run_extra = not args.no_extra and not args.sweep_t
+    run_extra = args.full and not args.no_extra and not args.sweep_t
     # ---- config[3] for real, every rank takes part: whole model on this rank's image shard + all-gather of the detections
     if run_extra and not args.no_dp_e2e and not wl["spike_rates"]:
         side_leg("dp_e2e", lambda: dp_e2e_leg(model_for("bdd", 11), dev, rank, world, fence))   # (same seed: same weights on every rank)

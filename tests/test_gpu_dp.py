@@ -16,7 +16,7 @@ def test_bench_self_launches_two_ranks_on_one_device(gpu_device):
     env = dict(os.environ, SNN_DIST_BACKEND="gloo", SNN_DP_DEVICE="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--inputs", "randn", "--no-extra", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
+                        "--inputs", "randn", "--full", "--no-extra", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

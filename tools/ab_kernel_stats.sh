@@ -7,7 +7,7 @@ for round in 1 2 3; do
   for n in "$@"; do
     if [ $n = product ]; then unset SNN_HIP_LIB; else export SNN_HIP_LIB=$PWD/tools/_ab/lib_$n.so; fi
     d=$OUT/${n}_$round
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra --no-clock-probe ${BENCH_ARGS:-} > $d.log 2>&1
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra --no-clock-probe ${BENCH_ARGS:-} > $d.log 2>&1
     f=$(find $d -name "*kernel_stats.csv" | head -1)
     [ -n "$f" ] && python3 - "$f" "$PAT" $n $round <<'PY'
 import csv, re, sys

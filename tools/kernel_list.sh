@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_list
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-alt "$@" > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-alt "$@" > $OUT/stats.log 2>&1
 python3 - <<PY
 import csv, glob
 f = sorted(glob.glob("$OUT/stats/*/*_kernel_stats.csv"))[-1]
