@@ -1810,10 +1810,14 @@ size_t snn_rpn_head_workspace_bytes(const snn_rpn_level* lv, int n_levels, int C
     return tot;
 }
 
-int snn_rpn_head_forward_stages(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
-                                const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
-                                float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
-                                float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, snn_stream_t stream) {
+// an RPN pass with any-time readouts (snn_rpn_head_forward_readouts): outputs [n][P][A] / [n][P][4A], counts [n][n_levels][max_n]
+struct RpnReadouts { const int* steps; int n; };
+
+// the RPN head: encoder, conv + LIF, then the LI heads - one readout at T (the plain forward), or the readout set with its spike counts
+static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
+                         const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                         float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                         float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, const RpnReadouts* ro, snn_stream_t stream) {
     if (!lv || !p || !w_shared_packed || !w_heads_packed || !out_logits || !out_bbox || !ws)
         return fail(-1, "snn_rpn_head_forward: null argument");
     if (n_levels <= 0 || n_levels > SNN_MAX_LEVELS) return fail(-1, "snn_rpn_head_forward: n_levels=%d", n_levels);
@@ -1921,45 +1925,17 @@ int snn_rpn_head_forward_stages(const snn_rpn_level* lv, int n_levels, int C, in
     }
     g_last_rpn_planes[0] = o_spk; g_last_rpn_planes[1] = split ? 1 : 0; g_last_rpn_planes[2] = (unsigned long long)P;
     if (!(stage_mask & SNN_STAGE_LI_HEADS)) return 0;
-    return li_heads_impl(spk, stride, T, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox, sum_logits,
-                         sum_bbox, split, stream);
-}
-
-int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
-                         const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
-                         float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
-                         void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return snn_rpn_head_forward_stages(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits,
-                                       out_bbox, spike_counts, sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL,
-                                       stream);
-}
-
-int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,
-                                  const snn_params* p, const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
-                                  float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
-                                  void* ws, size_t ws_bytes, snn_stream_t stream) {
-    if (check_steps(steps, n_steps, "snn_rpn_head_forward_readouts")) return -1;
-    if ((sum_logits == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_rpn_head_forward_readouts: sum_logits and sum_bbox go together");
-    const int T = steps[n_steps - 1];
-    // encoder + conv + LIF of the T pass (all its argument checks); the heads and counts then read the planes it left.  Spike-rate
-    // readouts run the conv as a spike-rate forward at T (same launch); its counts go to the first rows of spike_counts, zeroed below
-    int rc = snn_rpn_head_forward_stages(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, nullptr,
-                                         nullptr, ws, ws_bytes, SNN_STAGE_ENCODE | SNN_STAGE_CONV_LIF, stream);
-    if (rc) return rc;
-    int max_n = 0;
-    const long long P = rpn_positions(lv, n_levels, &max_n);
-    const int Cw = cdiv(C, 32);
-    const bool split = g_last_rpn_planes[1] != 0;
-    const uint32_t* spk = (const uint32_t*)((const char*)ws + g_last_rpn_planes[0]);
-    const size_t stride = (size_t)P * Cw;
-    rc = li_heads_readouts_impl(spk, stride, steps, n_steps, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox, sum_logits,
-                                sum_bbox, split, stream);
+    if (!ro)
+        return li_heads_impl(spk, stride, T, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox, sum_logits,
+                             sum_bbox, split, stream);
+    int rc = li_heads_readouts_impl(spk, stride, ro->steps, ro->n, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox,
+                                    sum_logits, sum_bbox, split, stream);
     if (rc || !spike_counts) return rc;
-    // [n][n_levels][max_n]: popcounts of the shared LIF's planes t < T'_j per (level, image)
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * n_steps * n_levels * max_n, s) != hipSuccess)
+    // [n][n_levels][max_n]: popcounts of the shared LIF's planes t < T'_j per (level, image).  The conv above ran as a spike-rate
+    // forward at T (same launch) and left its counts in the first rows of spike_counts: zeroed and overwritten here
+    if (hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * ro->n * n_levels * max_n, s) != hipSuccess)
         return fail(-3, "hipMemsetAsync failed");
-    const StepList st = step_list(steps, n_steps);
+    const StepList st = step_list(ro->steps, ro->n);
     long long pb = 0;
     for (int l = 0; l < n_levels; ++l) {
         const int hw = lv[l].H * lv[l].W;
@@ -1971,6 +1947,33 @@ int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, 
         pb += (long long)lv[l].N * hw;
     }
     return 0;
+}
+
+int snn_rpn_head_forward_stages(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
+                                const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                                float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, snn_stream_t stream) {
+    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
+                         sum_bbox, ws, ws_bytes, stage_mask, nullptr, stream);
+}
+
+int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
+                         const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                         float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
+                         void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
+                         sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, nullptr, stream);
+}
+
+int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,
+                                  const snn_params* p, const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                                  float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
+                                  void* ws, size_t ws_bytes, snn_stream_t stream) {
+    if (check_steps(steps, n_steps, "snn_rpn_head_forward_readouts")) return -1;
+    if ((sum_logits == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_rpn_head_forward_readouts: sum_logits and sum_bbox go together");
+    const RpnReadouts ro{steps, n_steps};
+    return rpn_head_impl(lv, n_levels, C, A, steps[n_steps - 1], p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts,
+                         sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, &ro, stream);
 }
 
 // ---- finished spike-rate tensors -------------------------------------------------------------------
@@ -2249,6 +2252,53 @@ static bool det_planes_wm(const snn_params* p, const DetWindows& w) { return det
 // a detector pass with any-time readouts (snn_det_head_forward_readouts): outputs [n][R][K] / [n][R][K4], counts [n][R]
 struct DetReadouts { const int* steps; int n; uint32_t *c6, *c7; };
 
+// the readout entry points' own checks, before those of the pass: the step list, then the arguments that go in pairs
+static int det_readouts(const char* who, const int* steps, int n, uint32_t* c6, uint32_t* c7, const float* sum_cls, const float* sum_bbox,
+                        DetReadouts* ro) {
+    if (check_steps(steps, n, who)) return -1;
+    if ((c6 == nullptr) != (c7 == nullptr)) return fail(-1, "%s: spk6_count and spk7_count go together", who);
+    if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "%s: sum_cls and sum_bbox go together", who);
+    *ro = DetReadouts{steps, n, c6, c7};
+    return 0;
+}
+
+// what a detector pass decides before its encoder launch, whichever feed (rows or RoIAlign) it has
+struct DetPlan {
+    size_t o_enc, o_cur, o_s6, o_s7;     // det_ws_layout
+    size_t o_raw;                        // where the unfolded encoder writes: o_enc, or the last region for permuted fc6 weights (det_ws_perm_offset)
+    DetWindows win;
+    bool wm, per;                        // encoder planes word-major (det_planes_wm); fc6 on the encoder's period planes (snn_common.h)
+};
+static int det_plan(const char* who, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, bool spike_rates, bool wm_ok,
+                    size_t ws_bytes, DetPlan* dp) {
+    size_t need;
+    det_ws_layout(R, D, Hd, T, &dp->o_enc, &dp->o_cur, &dp->o_s6, &dp->o_s7, &need);
+    if (ws_bytes < need) return fail(-2, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    if (check_T(T, who)) return -1;
+    dp->o_raw = w6_inner > 1 ? det_ws_perm_offset(R, D, Hd, T) : dp->o_enc;
+    dp->win = det_windows(p, T, spike_rates);
+    dp->wm = det_planes_wm(p, dp->win) && wm_ok;
+    dp->per = knobs().periods && periods_possible(p) && det_b3_tiles(p, dp->win);
+    return 0;
+}
+
+// rounds 5 / 6: where fc6 will run the structured-sparse launch on bin-major planes, ONE encoder launch writes them - permuted, e_3 ..
+// compressed - instead of encoder + k_permute_planes + k_compress_planes.  fc6's own launcher is asked (nothing is enqueued).  feed_ok:
+// the feed's own conditions; *np, *eth: the folded encoder's neuron and threshold table
+static bool det_fc6_folds(bool feed_ok, const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
+                          uint32_t* spk6_count, void* ws, snn_stream_t stream, NeuronP* np, const EncTh** eth) {
+    if (!knobs().enc_fold || !feed_ok || w6_inner != 49 || !dp.wm || !dp.per) return false;
+    *np = make_p(p, p->v_th_enc);
+    np->v_fire = ENC_FIRED;
+    if (!enc_zero_rest(*np) || enc_mode(*np, eth) != ENC_QUANT) return false;
+    Gemm3Args a6;
+    G3Tile t6;
+    return spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)ws + dp.o_enc), T, R, D, Hd, p, (const uint16_t*)w6_packed,
+                                      (uint32_t*)((char*)ws + dp.o_s6), (size_t)R * cdiv(Hd, 32), spk6_count, true, true, &dp.win.fc6, true,
+                                      &a6, &t6) == 0 &&
+           gemm3_lif_sparse(a6, false, (char*)ws + dp.o_cur, dp.o_s6 - dp.o_cur, (hipStream_t)stream, SPARSE_QUERY) == 1;
+}
+
 // the LI heads at the end of a detector pass: one readout at T (the plain forward), or the readout set with its spike counts
 static int det_heads_tail(const uint32_t* s6, const uint32_t* s7, int R, int Hd, int K, int K4, int T, const snn_params* p, const float* w_heads_packed,
                           float* out_cls, float* out_bbox, float* sum_cls, float* sum_bbox, bool s6_wm, const DetReadouts* ro, snn_stream_t stream) {
@@ -2268,12 +2318,12 @@ static int det_heads_tail(const uint32_t* s6, const uint32_t* s7, int R, int Hd,
 static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, const snn_params* p, const void* w6_packed,
                                 const void* w7_packed, const float* w_heads_packed, float* out_cls, float* out_bbox,
                                 uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws,
-                                bool enc_wm, const DetWindows& win, bool enc_periods, snn_stream_t stream, int k_inner = 0, bool folded = false,
-                                const DetReadouts* ro = nullptr) {
+                                const DetPlan& dp, snn_stream_t stream, int k_inner, bool folded, const DetReadouts* ro) {
     // folded (round 5): the encoder launch already wrote the planes in fc6's permuted order, e_3 .. compressed (k_encode_rows_perm): no
     // k_permute_planes, no k_compress_planes - fc6 must then run the structured-sparse launch (it was asked beforehand)
-    size_t o_enc, o_cur, o_s6, o_s7, need;
-    det_ws_layout(R, D, Hd, T, &o_enc, &o_cur, &o_s6, &o_s7, &need);
+    const size_t o_enc = dp.o_enc, o_cur = dp.o_cur, o_s6 = dp.o_s6, o_s7 = dp.o_s7;
+    const DetWindows& win = dp.win;
+    const bool enc_wm = dp.wm, enc_periods = dp.per;
     hipStream_t s = (hipStream_t)stream;
     uint32_t* enc = (uint32_t*)((char*)ws + o_enc);
     float* cur = (float*)((char*)ws + o_cur);
@@ -2290,7 +2340,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
             return fail(-4, "snn_det_head_forward: permuted fc6 weights (inner = %d) need D = C * inner, C %% 32 == 0 and the fused bf16x3 path", k_inner);
         // (the encoder wrote its planes into the LAST region of the workspace; the permuted ones go to the front, where fc6 reads them -
         // the sparse kernel addresses its side buffers as 32-bit offsets from the planes, so these must lie in front of them)
-        const uint32_t* enc_raw = (const uint32_t*)((char*)ws + det_ws_perm_offset(R, D, Hd, T));
+        const uint32_t* enc_raw = (const uint32_t*)((char*)ws + dp.o_raw);
         const int Dw = cdiv(D, 32);
         if (k_inner != 49) return fail(-4, "snn_det_head_forward: permuted fc6 weights: inner = %d (only 49 = 7 x 7 bins is built)", k_inner);
         hipLaunchKernelGGL(k_permute_planes<49>, dim3(cdiv(R, 32), win.enc_steps), dim3(256), 0, s, enc_raw, enc, Dw, R, C);
@@ -2346,41 +2396,6 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
                           stream);                                                                       // :505-510
 }
 
-int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
-                         const void* w6_packed, const void* w7_packed, const float* w_heads_packed,
-                         float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
-                         float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return snn_det_head_forward_k(x, R, D, Hd, K, K4, T, p, w6_packed, 0, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count,
-                                  sum_cls, sum_bbox, ws, ws_bytes, stream);
-}
-
-static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
-                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
-                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
-                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream, const DetReadouts* ro);
-
-int snn_det_head_forward_k(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
-                           const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
-                           float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
-                           float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
-                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
-}
-
-int snn_det_head_forward_readouts(const float* x, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps, const snn_params* p,
-                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
-                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
-                                  float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    if (check_steps(steps, n_steps, "snn_det_head_forward_readouts")) return -1;
-    if ((spk6_count == nullptr) != (spk7_count == nullptr)) return fail(-1, "snn_det_head_forward_readouts: spk6_count and spk7_count go together");
-    if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_det_head_forward_readouts: sum_cls and sum_bbox go together");
-    // spike-rate readouts: the pass runs as a spike-rate forward at T (same launches, windows of every lif6 step); its per-RoI counts land in
-    // the first rows of the count buffers, which the readout counts then overwrite in stream order
-    const DetReadouts ro{steps, n_steps, spk6_count, spk7_count};
-    return det_head_forward_impl(x, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, &ro);
-}
-
 static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
@@ -2388,33 +2403,17 @@ static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, in
     if (!x || !p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
         return fail(-1, "snn_det_head_forward: null argument");
     if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward: bad shape");
-    if (check_T(T, "snn_det_head_forward")) return -1;
-    size_t o_enc, o_cur, o_s6, o_s7, need;
-    det_ws_layout(R, D, Hd, T, &o_enc, &o_cur, &o_s6, &o_s7, &need);
-    if (ws_bytes < need) return fail(-2, "snn_det_head_forward: workspace %zu < %zu bytes", ws_bytes, need);
-    const DetWindows win = det_windows(p, T, spk6_count != nullptr);
-    const bool wm = det_planes_wm(p, win) && encode_rows_wm_ok(x, D);
-    const bool per = knobs().periods && periods_possible(p) && det_b3_tiles(p, win);      // fc6 on the encoder's period planes (snn_common.h)
-    if (w6_inner > 1 && !wm) return fail(-4, "snn_det_head_forward: permuted fc6 weights need the word-major fused bf16x3 path (D %% 32 == 0, x 16-byte aligned)");
-    // round 5: where fc6 will run the structured-sparse launch on bin-major planes, ONE encoder launch writes them - permuted, e_3 .. compressed
-    // (k_encode_rows_perm) - instead of encoder + k_permute_planes + k_compress_planes.  fc6's own launcher is asked (nothing is enqueued).
-    bool fold = false;
-    const EncTh* eth_f = nullptr;
-    if (knobs().enc_fold && w6_inner == 49 && wm && per && D % (49 * 64) == 0) {
-        NeuronP npq = make_p(p, p->v_th_enc);
-        npq.v_fire = ENC_FIRED;
-        if (enc_zero_rest(npq) && enc_mode(npq, &eth_f) == ENC_QUANT) {
-            Gemm3Args a6;
-            G3Tile t6;
-            const int Hw = cdiv(Hd, 32);
-            if (spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)ws + o_enc), T, R, D, Hd, p, (const uint16_t*)w6_packed, (uint32_t*)((char*)ws + o_s6), (size_t)R * Hw,
-                                           spk6_count, true, true, &win.fc6, true, &a6, &t6) == 0)
-                fold = gemm3_lif_sparse(a6, false, (char*)ws + o_cur, o_s6 - o_cur, (hipStream_t)stream, SPARSE_QUERY) == 1;
-        }
-    }
+    if (check_T(T, "snn_det_head_forward")) return -1;          // (the row-fed entry points check T before the workspace)
+    DetPlan dp;
     int rc;
+    if ((rc = det_plan("snn_det_head_forward", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, encode_rows_wm_ok(x, D), ws_bytes, &dp)))
+        return rc;
+    if (w6_inner > 1 && !dp.wm) return fail(-4, "snn_det_head_forward: permuted fc6 weights need the word-major fused bf16x3 path (D %% 32 == 0, x 16-byte aligned)");
+    NeuronP np;
+    const EncTh* eth_f = nullptr;
+    const bool fold = det_fc6_folds(D % (49 * 64) == 0, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
     if (fold) {
-        const int Te = win.enc_steps, C = D / 49;
+        const int Te = dp.win.enc_steps, C = D / 49;
         const int rb = knobs().encp_rb ? (knobs().encp_rb == 16 ? 16 : 8) : (Te <= ENCP_LDS_WORDS / (2 * 49 * 16) ? 16 : 8);     // (one pass through LDS where 16 RoIs per block allow it)
         const size_t lds = (size_t)min(Te, ENCP_LDS_WORDS / (2 * 49 * rb)) * 2 * 49 * rb * 4;
         // eight waves per block where only two blocks fit a CU's LDS (T_det = 12: -2 us, T_det = 24: -10 us), four where three fit (T_det = 16: eight
@@ -2424,19 +2423,97 @@ static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, in
                                     : (nw == 8 ? (const void*)k_encode_rows_perm<49, 8, 8> : (const void*)k_encode_rows_perm<49, 8, 4>);
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        uint32_t* planes_f = (uint32_t*)((char*)ws + o_enc);
-        uint32_t* cmp_f = (uint32_t*)((char*)ws + o_cur);
+        uint32_t* planes_f = (uint32_t*)((char*)ws + dp.o_enc);
+        uint32_t* cmp_f = (uint32_t*)((char*)ws + dp.o_cur);
         const int nd_f = 2;
         void* kargs[] = {(void*)&x, (void*)&R, (void*)&C, (void*)&Te, (void*)&nd_f, (void*)eth_f, (void*)&planes_f, (void*)&cmp_f};
         e = hipLaunchKernel(kern, dim3(cdiv(R, rb), C / 64), dim3(64 * nw), kargs, lds, (hipStream_t)stream);
         if (e != hipSuccess) return fail(-3, "k_encode_rows_perm launch failed: %s", hipGetErrorString(e));
         SNN_CHECK_LAUNCH("k_encode_rows_perm");
-    } else {
-        uint32_t* enc_dst = (uint32_t*)((char*)ws + (w6_inner > 1 ? det_ws_perm_offset(R, D, Hd, T) : o_enc));
-        if ((rc = encode_rows_impl(x, R, D, win.enc_steps, p, enc_dst, (size_t)R * cdiv(D, 32), wm, stream, per))) return rc;
+    } else if ((rc = encode_rows_impl(x, R, D, dp.win.enc_steps, p, (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), dp.wm, stream,
+                                      dp.per))) {
+        return rc;
     }
     return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold, ro);
+                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
+}
+
+static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                          snn_stream_t stream, const DetReadouts* ro) {
+    if (!p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
+        return fail(-1, "snn_det_head_forward_roialign: null argument");
+    if (R <= 0 || C <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward_roialign: bad shape");
+    const int D = C * 49;
+    DetPlan dp;
+    int rc;
+    if ((rc = det_plan("snn_det_head_forward_roialign", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, true, ws_bytes, &dp))) return rc;
+    if (w6_inner > 1 && (!dp.wm || w6_inner != 49)) return fail(-4, "snn_det_head_forward_roialign: permuted fc6 weights need inner = 49 and the word-major fused bf16x3 path");
+    // round 6: the RoIAlign encoder folds as the row encoder does since round 5 (k_roi_align_encode_perm).
+    // Planned for windows of up to 12 planes (T_det <= 14): measured on the bench's pyramid, 2000 RoIs (profiles/r6_roi_fold_ab.txt, same lease) the fused
+    // head takes 0.943 against 0.948 ms at T_det = 12 - the launch itself is 30 us slower than the table kernel (7 of 8 lanes per bin row, a second
+    // pass that transposes the ballots) and saves k_permute_planes + k_compress_planes (38 us) and their two 31-MB plane copies - but 2.04 against
+    // 1.88 ms at T_det = 24, where its 44 KB of LDS leave three work-groups per CU to a launch that lives on loads in flight.
+    bool feed_ok = knobs().roi_tab && dp.win.enc_steps <= 12 && C % 64 == 0 && levels_host && rois && roi_batch && roi_level && n_levels > 0 &&
+                   n_levels <= 4;
+    for (int l = 0; l < n_levels && feed_ok; ++l)
+        feed_ok = levels_host[l].feat && levels_host[l].H > 0 && levels_host[l].W >= 2 && (long long)C * levels_host[l].H * levels_host[l].W < (1ll << 29);
+    NeuronP np;
+    const EncTh* eth_f = nullptr;
+    const bool fold = det_fc6_folds(feed_ok, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
+    if (fold) {
+        constexpr int RW = 4;
+        RoiArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        for (int l = 0; l < n_levels; ++l) {
+            fa.lv[l].feat = levels_host[l].feat; fa.lv[l].H = levels_host[l].H; fa.lv[l].W = levels_host[l].W; fa.lv[l].scale = levels_host[l].spatial_scale;
+        }
+        fa.p = np; fa.quant = 1; fa.eth = *eth_f;
+        fa.rois = rois; fa.roi_batch = roi_batch; fa.roi_level = roi_level;
+        fa.planes = (uint32_t*)((char*)ws + dp.o_enc); fa.cmp = (uint32_t*)((char*)ws + dp.o_cur); fa.nd = 2;
+        fa.plane_stride = (unsigned long long)R * cdiv(D, 32); fa.R = R; fa.C = C; fa.T = dp.win.enc_steps; fa.Dw = cdiv(D, 32);
+        fa.RW = RW; fa.n_rg = cdiv(R, 4 * RW);
+        const int n_cp = C / 64, n_items = fa.n_rg * 7;
+        const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
+        hipLaunchKernelGGL(k_roi_align_encode_perm<RW>, dim3(grid), dim3(256), (size_t)fa.T * (7 + 8) * 4 * RW * 8, (hipStream_t)stream, fa);     // word pairs + raw ballots
+        SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
+    } else if ((rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, dp.win.enc_steps, p,
+                                           (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per))) {
+        return rc;
+    }
+    return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
+                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
+}
+
+int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                         const void* w6_packed, const void* w7_packed, const float* w_heads_packed,
+                         float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                         float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, 0, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count,
+                                 sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+}
+
+int snn_det_head_forward_k(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                           const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                           float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                           float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+}
+
+// spike-rate readouts: the pass runs as a spike-rate forward at T (same launches, windows of every lif6 step); its per-RoI counts land in
+// the first rows of the count buffers, which the readout counts then overwrite in stream order
+int snn_det_head_forward_readouts(const float* x, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps, const snn_params* p,
+                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                  float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    DetReadouts ro;
+    if (det_readouts("snn_det_head_forward_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
+    return det_head_forward_impl(x, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
+                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, &ro);
 }
 
 int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
@@ -2445,16 +2522,10 @@ int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels
                                   const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                   uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                   snn_stream_t stream) {
-    return snn_det_head_forward_roialign_k(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, 0, w7_packed,
-                                           w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
+    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, 0,
+                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
+                                          ws_bytes, stream, nullptr);
 }
-
-static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
-                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
-                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
-                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
-                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
-                                          snn_stream_t stream, const DetReadouts* ro);
 
 int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
                                     const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
@@ -2473,80 +2544,11 @@ int snn_det_head_forward_roialign_readouts(const snn_roi_level* levels_host, int
                                            const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                            uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                            snn_stream_t stream) {
-    if (check_steps(steps, n_steps, "snn_det_head_forward_roialign_readouts")) return -1;
-    if ((spk6_count == nullptr) != (spk7_count == nullptr))
-        return fail(-1, "snn_det_head_forward_roialign_readouts: spk6_count and spk7_count go together");
-    if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_det_head_forward_roialign_readouts: sum_cls and sum_bbox go together");
-    const DetReadouts ro{steps, n_steps, spk6_count, spk7_count};     // (as snn_det_head_forward_readouts)
+    DetReadouts ro;
+    if (det_readouts("snn_det_head_forward_roialign_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
     return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
                                           w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
                                           ws_bytes, stream, &ro);
-}
-
-static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
-                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
-                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
-                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
-                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
-                                          snn_stream_t stream, const DetReadouts* ro) {
-    if (!p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
-        return fail(-1, "snn_det_head_forward_roialign: null argument");
-    if (R <= 0 || C <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward_roialign: bad shape");
-    const int D = C * 49;
-    size_t o_enc, o_cur, o_s6, o_s7, need;
-    det_ws_layout(R, D, Hd, T, &o_enc, &o_cur, &o_s6, &o_s7, &need);
-    if (ws_bytes < need) return fail(-2, "snn_det_head_forward_roialign: workspace %zu < %zu bytes", ws_bytes, need);
-    if (check_T(T, "snn_det_head_forward_roialign")) return -1;
-    const DetWindows win = det_windows(p, T, spk6_count != nullptr);
-    const bool wm = det_planes_wm(p, win);
-    const bool per = knobs().periods && periods_possible(p) && det_b3_tiles(p, win);
-    if (w6_inner > 1 && (!wm || w6_inner != 49)) return fail(-4, "snn_det_head_forward_roialign: permuted fc6 weights need inner = 49 and the word-major fused bf16x3 path");
-    // round 6: where fc6 will run the structured-sparse launch on bin-major planes, the RoIAlign encoder writes them itself - permuted, e_3 .. compressed
-    // (k_roi_align_encode_perm) - as the row encoder does since round 5 (snn_det_head_forward_k).  fc6's own launcher is asked (nothing is enqueued).
-    bool fold = false;
-    RoiArgs fa;
-    // Planned for windows of up to 12 planes (T_det <= 14): measured on the bench's pyramid, 2000 RoIs (profiles/r6_roi_fold_ab.txt, same lease) the fused
-    // head takes 0.943 against 0.948 ms at T_det = 12 - the launch itself is 30 us slower than the table kernel (7 of 8 lanes per bin row, a second
-    // pass that transposes the ballots) and saves k_permute_planes + k_compress_planes (38 us) and their two 31-MB plane copies - but 2.04 against
-    // 1.88 ms at T_det = 24, where its 44 KB of LDS leave three work-groups per CU to a launch that lives on loads in flight.
-    if (knobs().enc_fold && knobs().roi_tab && win.enc_steps <= 12 && w6_inner == 49 && wm && per && C % 64 == 0 && levels_host && rois && roi_batch && roi_level && n_levels > 0 && n_levels <= 4) {
-        memset(&fa, 0, sizeof(fa));
-        bool ok = true;
-        for (int l = 0; l < n_levels && ok; ++l) {
-            ok = levels_host[l].feat && levels_host[l].H > 0 && levels_host[l].W >= 2 && (long long)C * levels_host[l].H * levels_host[l].W < (1ll << 29);
-            fa.lv[l].feat = levels_host[l].feat; fa.lv[l].H = levels_host[l].H; fa.lv[l].W = levels_host[l].W; fa.lv[l].scale = levels_host[l].spatial_scale;
-        }
-        fa.p = make_p(p, p->v_th_enc);
-        fa.p.v_fire = ENC_FIRED;
-        const EncTh* eth_f = nullptr;
-        if (ok && enc_zero_rest(fa.p) && enc_mode(fa.p, &eth_f) == ENC_QUANT) {
-            fa.quant = 1; fa.eth = *eth_f;
-            Gemm3Args a6;
-            G3Tile t6;
-            const int Hw = cdiv(Hd, 32);
-            if (spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)ws + o_enc), T, R, D, Hd, p, (const uint16_t*)w6_packed, (uint32_t*)((char*)ws + o_s6), (size_t)R * Hw,
-                                           spk6_count, true, true, &win.fc6, true, &a6, &t6) == 0)
-                fold = gemm3_lif_sparse(a6, false, (char*)ws + o_cur, o_s6 - o_cur, (hipStream_t)stream, SPARSE_QUERY) == 1;
-        }
-    }
-    if (fold) {
-        constexpr int RW = 4;
-        fa.rois = rois; fa.roi_batch = roi_batch; fa.roi_level = roi_level;
-        fa.planes = (uint32_t*)((char*)ws + o_enc); fa.cmp = (uint32_t*)((char*)ws + o_cur); fa.nd = 2;
-        fa.plane_stride = (unsigned long long)R * cdiv(D, 32); fa.R = R; fa.C = C; fa.T = win.enc_steps; fa.Dw = cdiv(D, 32);
-        fa.RW = RW; fa.n_rg = cdiv(R, 4 * RW);
-        const int n_cp = C / 64, n_items = fa.n_rg * 7;
-        const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
-        hipLaunchKernelGGL(k_roi_align_encode_perm<RW>, dim3(grid), dim3(256), (size_t)fa.T * (7 + 8) * 4 * RW * 8, (hipStream_t)stream, fa);     // word pairs + raw ballots
-        SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
-    } else {
-        uint32_t* enc_dst = (uint32_t*)((char*)ws + (w6_inner > 1 ? det_ws_perm_offset(R, D, Hd, T) : o_enc));
-        int rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, win.enc_steps, p,
-                                       enc_dst, (size_t)R * cdiv(D, 32), nullptr, wm, stream, per);
-        if (rc) return rc;
-    }
-    return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, wm, win, per, stream, w6_inner, fold, ro);
 }
 
 int snn_det_exchange_payload(const float* class_logits, const float* box_regression, int N, int rois_per_image, int K,

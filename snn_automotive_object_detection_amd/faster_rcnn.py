@@ -9,10 +9,10 @@ import os
 from torch import nn
 
 from . import ops
-from .rpn import _WeightCache, _pack_heads_unchecked, _strict_if_inexact, _warn_once_box
+from .rpn import _SpikingHead, _WeightCache, _pack_heads_unchecked, _per_precision
 
 
-class FastRCNNPredictorSNNFull(nn.Module):
+class FastRCNNPredictorSNNFull(_SpikingHead):
     """
     Spiking box head + predictor: ``num_steps`` x { encoder -> fc6 -> LIF -> fc7 -> LIF ->
     {cls_score -> LI, bbox_pred -> LI} } on the flattened RoI features.
@@ -42,44 +42,21 @@ class FastRCNNPredictorSNNFull(nn.Module):
         self.cls_score = nn.Linear(representation_size, num_classes, bias=False)    # :455
         self.only_one_bbox = only_one_bbox                                           # :460-467
         self.bbox_pred = nn.Linear(representation_size, 4 if only_one_bbox else num_classes * 4, bias=False)
-        self._c6 = {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache()}
-        self._c7 = {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache()}
+        self._c6 = _per_precision()
+        self._c7 = _per_precision()
         self._ch = _WeightCache()
         self._c6p = _WeightCache()              # fc6 in the permuted reduction order (fc6_inner)
-        self._cache_split = _WeightCache()      # None, or why these weights cannot be carried as three bf16 planes (-> "f32_strict")
-        self.last_spike_counts = None
 
-    def invalidate_packed_weights(self) -> None:
-        """drop the packed copies of the weights (needed after in-place edits through ``param.data``, which do not bump the
-        version counter the cache is keyed on); rebuilt on the next forward"""
-        for c in list(self._c6.values()) + list(self._c7.values()) + [self._ch, self._c6p, self._cache_split]:
-            c.invalidate()
+    def _caches(self):
+        return list(self._c6.values()) + list(self._c7.values()) + [self._ch, self._c6p]
 
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packed_weights()
-        return out
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self.invalidate_packed_weights()
+    def _split_weights(self, prec):
+        return (self.cls_score.weight, self.bbox_pred.weight) + ((self.fc6.weight, self.fc7.weight) if prec == "bf16x3" else ())
 
     def _eff_precision(self) -> str:
         if self.precision == "mxfp6" and (self.in_channels % 128 or self.representation_size % 128):
             return "bf16x3"
         return self.precision
-
-    def _params(self, precision=None):
-        return ops.make_params(self.p_enc, self.p_lif, self.dt, self.li_order, precision or self._resolve_precision())
-
-    def _resolve_precision(self) -> str:
-        """see RPNHeadSNN._resolve_precision: "f32_strict" (with a RuntimeWarning) where a weight does not split into three bf16
-        planes exactly"""
-        prec = self._eff_precision()
-        if prec == "f32_strict" or not self.fc6.weight.is_cuda:       # (CPU weights: forward raises anyway - no CPU path)
-            return prec
-        split = (self.cls_score.weight, self.bbox_pred.weight) + ((self.fc6.weight, self.fc7.weight) if prec == "bf16x3" else ())
-        return _strict_if_inexact(self, prec, self._cache_split.get(split, _warn_once_box(ops.split_problem)))
 
     def fc6_inner(self, prec=None) -> int:
         """49 when fc6's weights are packed in the permuted reduction order k' = bin * C + channel (include/snn_hip.h:
@@ -108,84 +85,60 @@ class FastRCNNPredictorSNNFull(nn.Module):
         wh = self._ch.get((self.cls_score.weight, self.bbox_pred.weight), _pack_heads_unchecked)
         return w6, w7, wh
 
-    @torch.no_grad()
-    def forward(self, x):
-        T = int(self.num_steps)
-        Hd, K = self.representation_size, self.num_classes
-        K4 = self.bbox_pred.weight.shape[0]
+    def _pass_args(self, width: int, got: str) -> dict:
+        """the shapes, parameters and packed weights every forward variant hands to ops (ValueError on a wrong input width)"""
         prec = self._resolve_precision()
         w6, w7, wh = self._packed(prec)
+        if width != self.in_channels:
+            raise ValueError("expected %d input features, got %s" % (self.in_channels, got))
+        return dict(Hd=self.representation_size, K=self.num_classes, K4=self.bbox_pred.weight.shape[0], p=self._params(prec),
+                    w6_packed=w6, w7_packed=w7, w_heads_packed=wh, spike_rates=self.spike_rates, w6_inner=self.fc6_inner(prec))
+
+    @torch.no_grad()
+    def forward(self, x):
         x = x.flatten(start_dim=1)                                     # :473
-        if x.shape[1] != self.in_channels:
-            raise ValueError("expected %d input features, got %d" % (self.in_channels, x.shape[1]))
-        out = ops.det_head_forward(x, Hd, K, K4, T, self._params(prec), w6, w7, wh, spike_rates=self.spike_rates, w6_inner=self.fc6_inner(prec))
-        return self._finish(out, x.shape[0], x.device)
+        out = ops.det_head_forward(x, T=int(self.num_steps), **self._pass_args(x.shape[1], "%d" % x.shape[1]))
+        return self._finish(out)
 
     @torch.no_grad()
     def forward_roialign(self, feats, scales, rois, roi_level):
         """Same head fed straight from the FPN maps: MultiScaleRoIAlign(7x7, sampling 2) is fused with the encoder
         (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2)."""
-        T = int(self.num_steps)
-        Hd, K = self.representation_size, self.num_classes
-        K4 = self.bbox_pred.weight.shape[0]
-        prec = self._resolve_precision()
-        w6, w7, wh = self._packed(prec)
-        if feats[0].shape[1] * 49 != self.in_channels:
-            raise ValueError("expected %d input features, got %d x 49" % (self.in_channels, feats[0].shape[1]))
-        out = ops.det_head_forward_roialign(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, Hd, K, K4, T,
-                                            self._params(prec), w6, w7, wh, spike_rates=self.spike_rates, w6_inner=self.fc6_inner(prec))
-        return self._finish(out, rois.shape[0], rois.device)
+        out = ops.det_head_forward_roialign(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, T=int(self.num_steps),
+                                            **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]))
+        return self._finish(out)
 
     @torch.no_grad()
     def forward_readouts(self, x, steps) -> dict:
         """Every T' of ``steps`` from ONE head pass at T = steps[-1]: {T': (class_logits, box_regression)}, or {T': rates} with
         ``spike_rates`` - each what ``forward`` returns for num_steps = T'.  ``num_steps`` is not touched."""
         steps = ops.check_steps(steps)
-        Hd, K = self.representation_size, self.num_classes
-        K4 = self.bbox_pred.weight.shape[0]
-        prec = self._resolve_precision()
-        w6, w7, wh = self._packed(prec)
         x = x.flatten(start_dim=1)
-        if x.shape[1] != self.in_channels:
-            raise ValueError("expected %d input features, got %d" % (self.in_channels, x.shape[1]))
-        out = ops.det_head_forward_readouts(x, Hd, K, K4, steps, self._params(prec), w6, w7, wh, spike_rates=self.spike_rates,
-                                            w6_inner=self.fc6_inner(prec))
+        out = ops.det_head_forward_readouts(x, steps=steps, **self._pass_args(x.shape[1], "%d" % x.shape[1]))
         return self._finish_readouts(out, steps)
 
     @torch.no_grad()
     def forward_roialign_readouts(self, feats, scales, rois, roi_level, steps) -> dict:
         """forward_roialign with a readout per T' of ``steps`` (see forward_readouts)"""
         steps = ops.check_steps(steps)
-        Hd, K = self.representation_size, self.num_classes
-        K4 = self.bbox_pred.weight.shape[0]
-        prec = self._resolve_precision()
-        w6, w7, wh = self._packed(prec)
-        if feats[0].shape[1] * 49 != self.in_channels:
-            raise ValueError("expected %d input features, got %d x 49" % (self.in_channels, feats[0].shape[1]))
-        out = ops.det_head_forward_roialign_readouts(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, Hd, K, K4, steps,
-                                                     self._params(prec), w6, w7, wh, spike_rates=self.spike_rates,
-                                                     w6_inner=self.fc6_inner(prec))
+        out = ops.det_head_forward_roialign_readouts(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, steps=steps,
+                                                     **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]))
         return self._finish_readouts(out, steps)
 
-    def _finish_readouts(self, out, steps):
-        cls, bbox, (c6, c7, s_c, s_b) = out
-        res = {}
-        for j, T in enumerate(steps):
-            if not self.spike_rates:
-                res[T] = (cls[j], bbox[j])
-                continue
-            rates = ops.det_rates((c6[j], c7[j], s_c[j], s_b[j]), self.in_channels, self.representation_size, self.num_classes,
-                                  self.bbox_pred.weight.shape[0], T, self.only_one_bbox)
-            res[T] = [rates[0], rates[1], rates[2], rates[3]]
-        return res
+    def _rates(self, extras, T):
+        """faster_rcnn.py:568-618: four [R, 2] = (rate, "FLOPs") tensors - lif6, lif7, cls_score, bbox_pred - finished by
+        snn_det_rates from the integer spike counts of the LIF epilogues and the time-summed LI membranes (one launch)"""
+        rates = ops.det_rates(extras, self.in_channels, self.representation_size, self.num_classes,
+                              self.bbox_pred.weight.shape[0], T, self.only_one_bbox)
+        return [rates[0], rates[1], rates[2], rates[3]]
 
-    def _finish(self, out, R, dev):
+    def _finish_readouts(self, out, steps):
+        cls, bbox, extras = out
+        return {T: self._rates(tuple(e[j] for e in extras), T) if self.spike_rates else (cls[j], bbox[j]) for j, T in enumerate(steps)}
+
+    def _finish(self, out):
         cls, bbox, extras = out
         if not self.spike_rates:
             return cls, bbox                                           # :513-516
-        # faster_rcnn.py:568-618: four [R, 2] = (rate, "FLOPs") tensors - lif6, lif7, cls_score, bbox_pred - finished by
-        # snn_det_rates from the integer spike counts of the LIF epilogues and the time-summed LI membranes (one launch)
         self.last_spike_counts = (extras[0], extras[1])
-        rates = ops.det_rates(extras, self.in_channels, self.representation_size, self.num_classes,
-                              self.bbox_pred.weight.shape[0], int(self.num_steps), self.only_one_bbox)
-        return [rates[0], rates[1], rates[2], rates[3]]
+        return self._rates(extras, int(self.num_steps))

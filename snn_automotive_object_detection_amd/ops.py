@@ -467,12 +467,8 @@ _WS = _Workspace()
 _WS_RATES = _Workspace()                     # partial sums of snn_rpn_rates (must not alias the heads' workspace)
 
 
-def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: snn_params,
-                     w_shared_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False,
-                     stage_mask: int = 7):
-    """Returns (out_logits [P,A], out_bbox [P,4A], level_rows, extras) — position-major outputs.
-    ``stage_mask`` (SNN_STAGE_*: 1 encode, 2 conv+LIF, 4 LI heads) is for profiling only."""
-    lib = _lib.load()
+def _rpn_levels(feats: Sequence[torch.Tensor], C_: int):
+    """checked fp32 feature maps [N, C_, H, W] -> (the maps, their snn_rpn_level table, output rows per level, largest N)"""
     if len(feats) == 0 or len(feats) > _lib.SNN_MAX_LEVELS:
         raise _lib.SnnHipError("RPN head takes 1..%d feature levels, got %d" % (_lib.SNN_MAX_LEVELS, len(feats)))
     feats = [_f32c(f) for f in feats]
@@ -480,63 +476,91 @@ def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: 
         _need_gpu(f, "feature map")
         if f.dim() != 4 or f.shape[1] != C_:
             raise _lib.SnnHipError("feature map must be [N,%d,H,W], got %s" % (C_, tuple(f.shape)))
-    dev = feats[0].device
-    lv = (snn_rpn_level * len(feats))()
-    rows = []
-    for l, f in enumerate(feats):
-        lv[l] = snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0)
-        rows.append(f.shape[0] * f.shape[2] * f.shape[3])
-    P = sum(rows)
-    max_n = max(f.shape[0] for f in feats)
-    ws_bytes = lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, T, p.precision)
-    ws = _WS.get(dev, ws_bytes)
-    out_logits = torch.empty((P, A), dtype=torch.float32, device=dev)
-    out_bbox = torch.empty((P, 4 * A), dtype=torch.float32, device=dev)
-    counts = sum_l = sum_b = rates = None
+    lv = (snn_rpn_level * len(feats))(*[snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0) for f in feats])
+    rows = [f.shape[0] * f.shape[2] * f.shape[3] for f in feats]
+    return feats, lv, rows, max(f.shape[0] for f in feats)
+
+
+def _rpn_outputs(P: int, A: int, n_levels: int, max_n: int, spike_rates: bool, dev, n=None):
+    """out_logits [P, A], out_bbox [P, 4A], (counts [n_levels, max_n], sum_logits, sum_bbox) - None but with spike_rates;
+    each [n, ...] for n readouts"""
+    lead = () if n is None else (n,)
+    out_l = torch.empty(lead + (P, A), dtype=torch.float32, device=dev)
+    out_b = torch.empty(lead + (P, 4 * A), dtype=torch.float32, device=dev)
+    counts = sum_l = sum_b = None
     if spike_rates:
-        counts = torch.empty((len(feats), max_n), dtype=torch.int64, device=dev)
-        sum_l = torch.empty_like(out_logits)
-        sum_b = torch.empty_like(out_bbox)
+        counts = torch.empty(lead + (n_levels, max_n), dtype=torch.int64, device=dev)
+        sum_l, sum_b = torch.empty_like(out_l), torch.empty_like(out_b)
+    return out_l, out_b, (counts, sum_l, sum_b)
+
+
+def _rpn_rates(lib, lv, n_levels: int, C_: int, A: int, T: int, max_n: int, counts, sum_l, sum_b, dev) -> torch.Tensor:
+    """the finished [n_levels, 3, max_n, 2] = (rate, FLOPs) rows of rpn.py:171-195: two small launches, no torch arithmetic"""
+    rates = torch.empty((n_levels, 3, max_n, 2), dtype=torch.float32, device=dev)
+    rws = _WS_RATES.get(dev, lib.snn_rpn_rates_workspace_bytes(n_levels, max_n))
+    _lib.check(lib.snn_rpn_rates(lv, n_levels, C_, A, T, _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(rates), _ptr(rws),
+                                 rws.numel(), _stream()), "snn_rpn_rates")
+    return rates
+
+
+def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: snn_params,
+                     w_shared_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False,
+                     stage_mask: int = 7):
+    """Returns (out_logits [P,A], out_bbox [P,4A], level_rows, extras) — position-major outputs.
+    ``stage_mask`` (SNN_STAGE_*: 1 encode, 2 conv+LIF, 4 LI heads) is for profiling only."""
+    lib = _lib.load()
+    feats, lv, rows, max_n = _rpn_levels(feats, C_)
+    dev = feats[0].device
+    ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, T, p.precision))
+    out_logits, out_bbox, (counts, sum_l, sum_b) = _rpn_outputs(sum(rows), A, len(feats), max_n, spike_rates, dev)
     _lib.check(lib.snn_rpn_head_forward_stages(lv, len(feats), C_, A, T, C.byref(p), _ptr(w_shared_packed),
                                                _ptr(w_heads_packed), _ptr(out_logits), _ptr(out_bbox),
                                                _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(),
                                                int(stage_mask), _stream()),
                "snn_rpn_head_forward")
+    rates = None
     if spike_rates and stage_mask == 7:
-        # the finished [.., 2] = (rate, FLOPs) rows of rpn.py:171-195: two small launches, no torch arithmetic
-        rates = torch.empty((len(feats), 3, max_n, 2), dtype=torch.float32, device=dev)
-        rws = _WS_RATES.get(dev, lib.snn_rpn_rates_workspace_bytes(len(feats), max_n))
-        _lib.check(lib.snn_rpn_rates(lv, len(feats), C_, A, T, _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(rates), _ptr(rws),
-                                     rws.numel(), _stream()), "snn_rpn_rates")
+        rates = _rpn_rates(lib, lv, len(feats), C_, A, T, max_n, counts, sum_l, sum_b, dev)
     return out_logits, out_bbox, rows, (counts, sum_l, sum_b, rates)
+
+
+def _det_rows(x: torch.Tensor) -> torch.Tensor:
+    """box features -> fp32 rows [R, D] (a view at an odd offset is copied: the word-major encoder loads 16-byte pieces)"""
+    _need_gpu(x, "box features")
+    x = _f32c(x).flatten(1)
+    return x.clone() if x.data_ptr() % 16 else x
+
+
+def _det_outputs(R: int, K: int, K4: int, spike_rates: bool, dev, n=None):
+    """out_cls [R, K], out_bbox [R, K4], (c6 [R], c7 [R], sum_cls, sum_bbox) - None but with spike_rates; each [n, ...] for n readouts"""
+    lead = () if n is None else (n,)
+    out_cls = torch.empty(lead + (R, K), dtype=torch.float32, device=dev)
+    out_bbox = torch.empty(lead + (R, K4), dtype=torch.float32, device=dev)
+    c6 = c7 = s_c = s_b = None
+    if spike_rates:
+        c6 = torch.empty(lead + (R,), dtype=torch.int32, device=dev)
+        c7 = torch.empty(lead + (R,), dtype=torch.int32, device=dev)
+        s_c, s_b = torch.empty_like(out_cls), torch.empty_like(out_bbox)
+    return out_cls, out_bbox, (c6, c7, s_c, s_b)
+
+
+def _det_ws(lib, dev, R: int, D: int, Hd: int, K: int, K4: int, T: int, p: snn_params) -> torch.Tensor:
+    return _WS.get(dev, lib.snn_det_head_workspace_bytes(R, D, Hd, K, K4, T, p.precision))
 
 
 def det_head_forward(x: torch.Tensor, Hd: int, K: int, K4: int, T: int, p: snn_params, w6_packed: torch.Tensor,
                      w7_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False, w6_inner: int = 0):
     lib = _lib.load()
-    _need_gpu(x, "box features")
-    x = _f32c(x).flatten(1)
-    if x.data_ptr() % 16:                                        # (a view at an odd offset: the word-major encoder loads 16-byte pieces)
-        x = x.clone()
+    x = _det_rows(x)
     R, D = x.shape
-    dev = x.device
-    out_cls = torch.empty((R, K), dtype=torch.float32, device=dev)
-    out_bbox = torch.empty((R, K4), dtype=torch.float32, device=dev)
-    c6 = c7 = s_c = s_b = None
-    if spike_rates:
-        c6 = torch.empty((R,), dtype=torch.int32, device=dev)
-        c7 = torch.empty((R,), dtype=torch.int32, device=dev)
-        s_c = torch.empty_like(out_cls)
-        s_b = torch.empty_like(out_bbox)
-    if R == 0:
-        return out_cls, out_bbox, (c6, c7, s_c, s_b)
-    ws_bytes = lib.snn_det_head_workspace_bytes(R, D, Hd, K, K4, T, p.precision)
-    ws = _WS.get(dev, ws_bytes)
-    _lib.check(lib.snn_det_head_forward_k(_ptr(x), R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                          _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7),
-                                          _ptr(s_c), _ptr(s_b), _ptr(ws), ws.numel(), _stream()),
-               "snn_det_head_forward")
-    return out_cls, out_bbox, (c6, c7, s_c, s_b)
+    out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, x.device)
+    if R:
+        ws = _det_ws(lib, x.device, R, D, Hd, K, K4, T, p)
+        _lib.check(lib.snn_det_head_forward_k(_ptr(x), R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
+                                              _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
+                                              _ptr(ws), ws.numel(), _stream()),
+                   "snn_det_head_forward")
+    return out_cls, out_bbox, extras
 
 
 def det_rates(extras, D: int, Hd: int, K: int, K4: int, T: int, only_one_bbox: bool) -> torch.Tensor:
@@ -554,15 +578,16 @@ def det_rates(extras, D: int, Hd: int, K: int, K4: int, T: int, only_one_bbox: b
 # ---------------------------------------------------------------------------------------------
 # RoIAlign fused with the detector encoder
 # ---------------------------------------------------------------------------------------------
-def _roi_levels(feats, scales):
-    lv = (snn_roi_level * len(feats))()
-    keep = []
-    for i, (f, sc) in enumerate(zip(feats, scales)):
+def _roi_feed(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor, roi_level: torch.Tensor):
+    """the RoIAlign feed: (snn_roi_level table, the fp32 maps it points to, channels, rois [R, 4] fp32, roi_batch, roi_level int32)"""
+    keep, lvs = [], []
+    for f, sc in zip(feats, scales):
         _need_gpu(f, "feature map")
-        f = _f32c(f)
-        keep.append(f)
-        lv[i] = snn_roi_level(f.data_ptr(), f.shape[2], f.shape[3], float(sc), 0)
-    return lv, keep
+        keep.append(_f32c(f))
+        lvs.append(snn_roi_level(keep[-1].data_ptr(), f.shape[2], f.shape[3], float(sc), 0))
+    lv = (snn_roi_level * len(lvs))(*lvs)
+    return (lv, keep, keep[0].shape[1], _f32c(rois), roi_batch.to(torch.int32).contiguous(),
+            roi_level.to(torch.int32).contiguous())
 
 
 def roi_align_encode(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor, roi_level: torch.Tensor, T: int,
@@ -570,11 +595,7 @@ def roi_align_encode(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor,
     """feats: list of [N,C,H,W]; rois [R,4]; roi_batch/roi_level int32 [R] -> encoder planes int32 [T, R, Dw]
     (+ the pooled [R, C*49] features when asked: parity tests)"""
     lib = _lib.load()
-    lv, keep = _roi_levels(feats, scales)
-    Cc = keep[0].shape[1]
-    rois = _f32c(rois)
-    roi_batch = roi_batch.to(torch.int32).contiguous()
-    roi_level = roi_level.to(torch.int32).contiguous()
+    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
     Dw = cdiv(Cc * 49, 32)
     planes = torch.empty((T, R, Dw), dtype=torch.int32, device=rois.device)
@@ -587,29 +608,16 @@ def roi_align_encode(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor,
 def det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, Hd: int, K: int, K4: int, T: int, p: snn_params,
                               w6_packed, w7_packed, w_heads_packed, spike_rates: bool = False, w6_inner: int = 0):
     lib = _lib.load()
-    lv, keep = _roi_levels(feats, scales)
-    Cc = keep[0].shape[1]
-    rois = _f32c(rois)
-    roi_batch = roi_batch.to(torch.int32).contiguous()
-    roi_level = roi_level.to(torch.int32).contiguous()
-    R, dev = rois.shape[0], rois.device
-    out_cls = torch.empty((R, K), dtype=torch.float32, device=dev)
-    out_bbox = torch.empty((R, K4), dtype=torch.float32, device=dev)
-    c6 = c7 = s_c = s_b = None
-    if spike_rates:
-        c6 = torch.empty((R,), dtype=torch.int32, device=dev)
-        c7 = torch.empty((R,), dtype=torch.int32, device=dev)
-        s_c = torch.empty_like(out_cls)
-        s_b = torch.empty_like(out_bbox)
-    if R == 0:
-        return out_cls, out_bbox, (c6, c7, s_c, s_b)
-    ws_bytes = lib.snn_det_head_workspace_bytes(R, Cc * 49, Hd, K, K4, T, p.precision)
-    ws = _WS.get(dev, ws_bytes)
-    _lib.check(lib.snn_det_head_forward_roialign_k(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K,
-                                                   K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed), _ptr(w_heads_packed),
-                                                   _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7), _ptr(s_c), _ptr(s_b),
-                                                   _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_roialign")
-    return out_cls, out_bbox, (c6, c7, s_c, s_b)
+    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
+    R = rois.shape[0]
+    out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, rois.device)
+    if R:
+        ws = _det_ws(lib, rois.device, R, Cc * 49, Hd, K, K4, T, p)
+        _lib.check(lib.snn_det_head_forward_roialign_k(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K,
+                                                       K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
+                                                       _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
+                                                       _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_roialign")
+    return out_cls, out_bbox, extras
 
 
 
@@ -662,52 +670,18 @@ def rpn_head_forward_readouts(feats: Sequence[torch.Tensor], C_: int, A: int, st
     (counts [n,levels,max_n], sum_l, sum_b, rates: list of [levels,3,max_n,2] per readout))"""
     steps = check_steps(steps)
     lib = _lib.load()
-    if len(feats) == 0 or len(feats) > _lib.SNN_MAX_LEVELS:
-        raise _lib.SnnHipError("RPN head takes 1..%d feature levels, got %d" % (_lib.SNN_MAX_LEVELS, len(feats)))
-    feats = [_f32c(f) for f in feats]
-    for f in feats:
-        _need_gpu(f, "feature map")
-        if f.dim() != 4 or f.shape[1] != C_:
-            raise _lib.SnnHipError("feature map must be [N,%d,H,W], got %s" % (C_, tuple(f.shape)))
-    dev, n = feats[0].device, len(steps)
-    lv = (snn_rpn_level * len(feats))()
-    rows = []
-    for l, f in enumerate(feats):
-        lv[l] = snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0)
-        rows.append(f.shape[0] * f.shape[2] * f.shape[3])
-    P, max_n = sum(rows), max(f.shape[0] for f in feats)
+    feats, lv, rows, max_n = _rpn_levels(feats, C_)
+    dev = feats[0].device
     ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, steps[-1], p.precision))
-    out_l = torch.empty((n, P, A), dtype=torch.float32, device=dev)
-    out_b = torch.empty((n, P, 4 * A), dtype=torch.float32, device=dev)
-    counts = sum_l = sum_b = None
-    if spike_rates:
-        counts = torch.empty((n, len(feats), max_n), dtype=torch.int64, device=dev)
-        sum_l, sum_b = torch.empty_like(out_l), torch.empty_like(out_b)
+    out_l, out_b, (counts, sum_l, sum_b) = _rpn_outputs(sum(rows), A, len(feats), max_n, spike_rates, dev, n=len(steps))
     st, ns = _steps_arg(steps)
     _lib.check(lib.snn_rpn_head_forward_readouts(lv, len(feats), C_, A, st, ns, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed),
                                                  _ptr(out_l), _ptr(out_b), _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(),
                                                  _stream()), "snn_rpn_head_forward_readouts")
     rates = None
     if spike_rates:
-        rates = []
-        rws = _WS_RATES.get(dev, lib.snn_rpn_rates_workspace_bytes(len(feats), max_n))
-        for j, T in enumerate(steps):
-            r = torch.empty((len(feats), 3, max_n, 2), dtype=torch.float32, device=dev)
-            _lib.check(lib.snn_rpn_rates(lv, len(feats), C_, A, T, _ptr(counts[j]), _ptr(sum_l[j]), _ptr(sum_b[j]), _ptr(r), _ptr(rws),
-                                         rws.numel(), _stream()), "snn_rpn_rates")
-            rates.append(r)
+        rates = [_rpn_rates(lib, lv, len(feats), C_, A, T, max_n, counts[j], sum_l[j], sum_b[j], dev) for j, T in enumerate(steps)]
     return out_l, out_b, rows, (counts, sum_l, sum_b, rates)
-
-
-def _det_readout_outputs(R, K, K4, n, spike_rates, dev):
-    out_cls = torch.empty((n, R, K), dtype=torch.float32, device=dev)
-    out_bbox = torch.empty((n, R, K4), dtype=torch.float32, device=dev)
-    c6 = c7 = s_c = s_b = None
-    if spike_rates:
-        c6 = torch.empty((n, R), dtype=torch.int32, device=dev)
-        c7 = torch.empty((n, R), dtype=torch.int32, device=dev)
-        s_c, s_b = torch.empty_like(out_cls), torch.empty_like(out_bbox)
-    return out_cls, out_bbox, (c6, c7, s_c, s_b)
 
 
 def det_head_forward_readouts(x: torch.Tensor, Hd: int, K: int, K4: int, steps, p: snn_params, w6_packed: torch.Tensor,
@@ -715,20 +689,15 @@ def det_head_forward_readouts(x: torch.Tensor, Hd: int, K: int, K4: int, steps, 
     """one detector head pass at T = steps[-1]: (out_cls [n,R,K], out_bbox [n,R,K4], (c6 [n,R], c7, sum_cls, sum_bbox))"""
     steps = check_steps(steps)
     lib = _lib.load()
-    _need_gpu(x, "box features")
-    x = _f32c(x).flatten(1)
-    if x.data_ptr() % 16:
-        x = x.clone()
+    x = _det_rows(x)
     R, D = x.shape
-    out_cls, out_bbox, extras = _det_readout_outputs(R, K, K4, len(steps), spike_rates, x.device)
-    if R == 0:
-        return out_cls, out_bbox, extras
-    ws = _WS.get(x.device, lib.snn_det_head_workspace_bytes(R, D, Hd, K, K4, steps[-1], p.precision))
-    c6, c7, s_c, s_b = extras
-    st, ns = _steps_arg(steps)
-    _lib.check(lib.snn_det_head_forward_readouts(_ptr(x), R, D, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                                 _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7), _ptr(s_c), _ptr(s_b),
-                                                 _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_readouts")
+    out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, x.device, n=len(steps))
+    if R:
+        ws = _det_ws(lib, x.device, R, D, Hd, K, K4, steps[-1], p)
+        st, ns = _steps_arg(steps)
+        _lib.check(lib.snn_det_head_forward_readouts(_ptr(x), R, D, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner),
+                                                     _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
+                                                     _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_readouts")
     return out_cls, out_bbox, extras
 
 
@@ -737,23 +706,17 @@ def det_head_forward_roialign_readouts(feats, scales, rois, roi_batch, roi_level
     """det_head_forward_readouts fed straight from the FPN maps (RoIAlign fused with the encoder)"""
     steps = check_steps(steps)
     lib = _lib.load()
-    lv, keep = _roi_levels(feats, scales)
-    Cc = keep[0].shape[1]
-    rois = _f32c(rois)
-    roi_batch = roi_batch.to(torch.int32).contiguous()
-    roi_level = roi_level.to(torch.int32).contiguous()
+    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
-    out_cls, out_bbox, extras = _det_readout_outputs(R, K, K4, len(steps), spike_rates, rois.device)
-    if R == 0:
-        return out_cls, out_bbox, extras
-    ws = _WS.get(rois.device, lib.snn_det_head_workspace_bytes(R, Cc * 49, Hd, K, K4, steps[-1], p.precision))
-    c6, c7, s_c, s_b = extras
-    st, ns = _steps_arg(steps)
-    _lib.check(lib.snn_det_head_forward_roialign_readouts(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4,
-                                                          st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                                          _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), _ptr(c6), _ptr(c7),
-                                                          _ptr(s_c), _ptr(s_b), _ptr(ws), ws.numel(), _stream()),
-               "snn_det_head_forward_roialign_readouts")
+    out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, rois.device, n=len(steps))
+    if R:
+        ws = _det_ws(lib, rois.device, R, Cc * 49, Hd, K, K4, steps[-1], p)
+        st, ns = _steps_arg(steps)
+        _lib.check(lib.snn_det_head_forward_roialign_readouts(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4,
+                                                              st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
+                                                              _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
+                                                              _ptr(ws), ws.numel(), _stream()),
+                   "snn_det_head_forward_roialign_readouts")
     return out_cls, out_bbox, extras
 
 # ---------------------------------------------------------------------------------------------

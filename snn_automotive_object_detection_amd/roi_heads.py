@@ -130,8 +130,7 @@ class RoIHeadsSNN(nn.Module):
         if self.training:
             raise NotImplementedError("inference only: training the RoI heads is out of scope (DESIGN.md §7)")
         pool, head = self.box_roi_pool, self.box_head_and_predictor
-        if (self.fuse_roi_align and hasattr(head, "forward_roialign") and hasattr(pool, "assign")
-                and tuple(pool.output_size) == (7, 7) and pool.sampling_ratio == 2):
+        if self._fuses_roi_align("forward_roialign"):
             # RoIAlign fused into the head's encoder kernel: same values as the two calls below
             feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
             head_out = head.forward_roialign(feats, scales, rois, lvl)
@@ -144,11 +143,17 @@ class RoIHeadsSNN(nn.Module):
         """the head call of ``forward`` with a readout per T_det of ``steps`` (one pass at steps[-1]; the fused RoIAlign path where
         ``forward`` takes it): {T_det: head output}"""
         pool, head = self.box_roi_pool, self.box_head_and_predictor
-        if (self.fuse_roi_align and hasattr(head, "forward_roialign_readouts") and hasattr(pool, "assign")
-                and tuple(pool.output_size) == (7, 7) and pool.sampling_ratio == 2):
+        if self._fuses_roi_align("forward_roialign_readouts"):
             feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
             return head.forward_roialign_readouts(feats, scales, rois, lvl, steps)
         return head.forward_readouts(pool(features, proposals, image_shapes), steps)
+
+    def _fuses_roi_align(self, method: str) -> bool:
+        """does the head call take the fused RoIAlign path: the head has ``method`` and the pool is the 7x7, sampling-2 RoIAlign
+        the fused kernel restates"""
+        pool, head = self.box_roi_pool, self.box_head_and_predictor
+        return bool(self.fuse_roi_align and hasattr(head, method) and hasattr(pool, "assign")
+                    and tuple(pool.output_size) == (7, 7) and pool.sampling_ratio == 2)
 
     def detections_from_head(self, head_out, proposals: List[Tensor], image_shapes: List[Tuple[int, int]]):
         """the part of ``forward`` after the head call: detections (or, in spike-rate mode, the head's rates)"""

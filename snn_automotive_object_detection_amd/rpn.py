@@ -61,7 +61,54 @@ def _strict_if_inexact(module, prec: str, box) -> str:
     return "f32_strict"
 
 
-class RPNHeadSNN(nn.Module):
+def _per_precision():
+    """one packed-weight cache per packing ("f32_strict" packs as "f32")"""
+    return {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache()}
+
+
+class _SpikingHead(nn.Module):
+    """what both spiking heads share: their packed-weight caches, dropped by ``_apply`` (.to() / .half() / .cuda()) and
+    ``load_state_dict``, and the precision a forward resolves to.  A head supplies ``_eff_precision()``, ``_caches()`` (its
+    packed-weight caches) and ``_split_weights(prec)`` (the weights that precision splits into three bf16 planes)."""
+
+    def __init__(self):
+        super().__init__()
+        self._cache_split = _WeightCache()      # None, or why these weights cannot be carried as three bf16 planes (-> "f32_strict")
+        self.last_spike_counts = None
+
+    def invalidate_packed_weights(self) -> None:
+        """drop the packed (bf16x3 / mxfp6 / f32 fragment-major) copies of the weights (needed after in-place edits through
+        ``param.data``, which do not bump the version counter the caches are keyed on); rebuilt on the next forward"""
+        for c in self._caches() + [self._cache_split]:
+            c.invalidate()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self.invalidate_packed_weights()
+        return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self.invalidate_packed_weights()
+
+    def _params(self, precision=None):
+        return ops.make_params(self.p_enc, self.p_lif, self.dt, self.li_order, precision or self._resolve_precision())
+
+    def _resolve_precision(self) -> str:
+        """``_eff_precision()`` unless a weight the kernels of that precision would split into three bf16 planes does not split
+        EXACTLY (ops.check_bf16x3_split: magnitudes with bits below 2^-133, values next to FLT_MAX, NaN / infinity): then
+        "f32_strict" - fp32 matrix cores and fp32 VALU heads, nothing is split - with one RuntimeWarning per weight version.
+        The verdict is cached with the packed weights (one host synchronisation per weight update)."""
+        prec = self._eff_precision()
+        if prec == "f32_strict":
+            return prec
+        split = self._split_weights(prec)
+        if not split[0].is_cuda:                                      # (CPU weights: forward raises anyway - no CPU path)
+            return prec
+        return _strict_if_inexact(self, prec, self._cache_split.get(split, _warn_once_box(ops.split_problem)))
+
+
+class RPNHeadSNN(_SpikingHead):
     """
     Spiking RPN head: per FPN level, ``num_steps`` x { LIF current encoder -> 3x3 conv -> LIF ->
     {1x1 conv -> LI (objectness), 1x1 conv -> LI (box deltas)} }; returns the last-step LI membranes.
@@ -98,43 +145,19 @@ class RPNHeadSNN(nn.Module):
         for layer in self.modules():                                  # rpn.py:78-82
             if isinstance(layer, nn.Conv2d):
                 torch.nn.init.normal_(layer.weight, std=0.01)
-        self._cache_shared = {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache()}
+        self._cache_shared = _per_precision()
         self._cache_heads = _WeightCache()
-        self._cache_split = _WeightCache()      # None, or why these weights cannot be carried as three bf16 planes (-> "f32_strict")
-        self.last_spike_counts = None
 
-    def invalidate_packed_weights(self) -> None:
-        """drop the packed (bf16x3 / mxfp6 / f32 fragment-major) copies of the weights; they are rebuilt on the next forward"""
-        for c in list(self._cache_shared.values()) + [self._cache_heads, self._cache_split]:
-            c.invalidate()
+    def _caches(self):
+        return list(self._cache_shared.values()) + [self._cache_heads]
 
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self.invalidate_packed_weights()
-        return out
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self.invalidate_packed_weights()
+    def _split_weights(self, prec):
+        return (self.conv_cls.weight, self.conv_bbox.weight) + ((self.shared_conv.weight,) if prec == "bf16x3" else ())
 
     def _eff_precision(self) -> str:
         if self.precision == "mxfp6" and self.in_channels % 128:
             return "bf16x3"
         return self.precision
-
-    def _params(self, precision=None):
-        return ops.make_params(self.p_enc, self.p_lif, self.dt, self.li_order, precision or self._resolve_precision())
-
-    def _resolve_precision(self) -> str:
-        """``_eff_precision()`` unless a weight the kernels of that precision would split into three bf16 planes does not split
-        EXACTLY (ops.check_bf16x3_split: magnitudes with bits below 2^-133, values next to FLT_MAX, NaN / infinity): then
-        "f32_strict" - fp32 matrix cores and fp32 VALU heads, nothing is split - with one RuntimeWarning per weight version.
-        The verdict is cached with the packed weights (one host synchronisation per weight update)."""
-        prec = self._eff_precision()
-        if prec == "f32_strict" or not self.shared_conv.weight.is_cuda:       # (CPU weights: forward raises anyway - no CPU path)
-            return prec
-        split = (self.conv_cls.weight, self.conv_bbox.weight) + ((self.shared_conv.weight,) if prec == "bf16x3" else ())
-        return _strict_if_inexact(self, prec, self._cache_split.get(split, _warn_once_box(ops.split_problem)))
 
     def _packed_shared(self, prec=None):
         prec = prec or self._resolve_precision()
@@ -142,31 +165,39 @@ class RPNHeadSNN(nn.Module):
                 "mxfp6": ops.pack_conv3x3_mx}[prec]
         return self._cache_shared["f32" if prec == "f32_strict" else prec].get((self.shared_conv.weight,), pack)
 
-    @torch.no_grad()
-    def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
-        C, A, T = self.in_channels, self.num_anchors, int(self.num_steps)
+    def _pass_args(self):
+        """(C, A, parameters, packed shared conv, packed LI heads) of one head pass"""
         prec = self._resolve_precision()
         w_shared = self._packed_shared(prec)
         w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
-        out_l, out_b, rows, (counts, sum_l, sum_b, rate_rows) = ops.rpn_head_forward(
-            list(x), C, A, T, self._params(prec), w_shared, w_heads, spike_rates=self.spike_rates)
+        return self.in_channels, self.num_anchors, self._params(prec), w_shared, w_heads
+
+    def _level_views(self, x, out_l, out_b, rows, rate_rows):
+        """what ``forward`` returns, per level, from the position-major outputs of one readout: physically NHWC; the NCHW view
+        is what the reference returns (rpn.py:118-119) and makes concat_box_prediction_layers' view/permute/reshape
+        (rpn.py:256-258) copy-free.  Spike rates (rpn.py:171-195): three [N, 2] = (rate, FLOPs) tensors per level, finished
+        by snn_rpn_rates (views, no torch math)"""
+        A = self.num_anchors
         logits, bbox_reg, rates = [], [], []
         pos = 0
         for l, f in enumerate(x):
             N, H, W = f.shape[0], f.shape[2], f.shape[3]
             n = rows[l]
-            # physically NHWC; the NCHW view is what the reference returns (rpn.py:118-119) and makes
-            # concat_box_prediction_layers' view/permute/reshape (rpn.py:256-258) copy-free
             logits.append(out_l[pos:pos + n].view(N, H, W, A).permute(0, 3, 1, 2))
             bbox_reg.append(out_b[pos:pos + n].view(N, H, W, 4 * A).permute(0, 3, 1, 2))
-            if self.spike_rates:                                      # rpn.py:171-195: three [N, 2] = (rate, FLOPs) tensors per
-                rates += [rate_rows[l, j, :N] for j in range(3)]      # level, finished by snn_rpn_rates (views, no torch math)
+            if self.spike_rates:
+                rates += [rate_rows[l, j, :N] for j in range(3)]
             pos += n
+        return (logits, bbox_reg, rates) if self.spike_rates else (logits, bbox_reg)
+
+    @torch.no_grad()
+    def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
+        C, A, p, w_shared, w_heads = self._pass_args()
+        out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward(
+            list(x), C, A, int(self.num_steps), p, w_shared, w_heads, spike_rates=self.spike_rates)
         if self.spike_rates:
             self.last_spike_counts = counts                           # [levels, N] int64: shared-LIF spikes (tests, energy report)
-            return logits, bbox_reg, rates
-        return logits, bbox_reg
-
+        return self._level_views(x, out_l, out_b, rows, rate_rows)
 
     @torch.no_grad()
     def forward_readouts(self, x: List[Tensor], steps) -> dict:
@@ -174,26 +205,11 @@ class RPNHeadSNN(nn.Module):
         {T': (logits, bbox_reg)} - with ``spike_rates``, {T': (logits, bbox_reg, rates)} - each what ``forward`` returns for
         num_steps = T' (include/snn_hip.h: snn_rpn_head_forward_readouts states what is bit-exact).  ``num_steps`` is not touched."""
         steps = ops.check_steps(steps)
-        C, A = self.in_channels, self.num_anchors
-        prec = self._resolve_precision()
-        w_shared = self._packed_shared(prec)
-        w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
-        out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward_readouts(
-            list(x), C, A, steps, self._params(prec), w_shared, w_heads, spike_rates=self.spike_rates)
-        res = {}
-        for j, T in enumerate(steps):
-            logits, bbox_reg, rates = [], [], []
-            pos = 0
-            for l, f in enumerate(x):
-                N, H, W = f.shape[0], f.shape[2], f.shape[3]
-                n = rows[l]
-                logits.append(out_l[j, pos:pos + n].view(N, H, W, A).permute(0, 3, 1, 2))
-                bbox_reg.append(out_b[j, pos:pos + n].view(N, H, W, 4 * A).permute(0, 3, 1, 2))
-                if self.spike_rates:
-                    rates += [rate_rows[j][l, k, :N] for k in range(3)]
-                pos += n
-            res[T] = (logits, bbox_reg, rates) if self.spike_rates else (logits, bbox_reg)
-        return res
+        C, A, p, w_shared, w_heads = self._pass_args()
+        out_l, out_b, rows, (_, _, _, rate_rows) = ops.rpn_head_forward_readouts(
+            list(x), C, A, steps, p, w_shared, w_heads, spike_rates=self.spike_rates)
+        return {T: self._level_views(x, out_l[j], out_b[j], rows, rate_rows[j] if self.spike_rates else None)
+                for j, T in enumerate(steps)}
 
 
 # ---------------------------------------------------------------------------------------------
