@@ -70,6 +70,13 @@ typedef struct snn_params {
                                     Where layers go whose weights snn_check_bf16x3_split reports as not exactly splittable (packed
                                     weights: the SNN_PRECISION_F32 ones) */
 
+#define SNN_PRECISION_BF16 4     /* the SNN_PRECISION_BF16X3 path on ONE bf16 weight plane: the packers (snn_pack_*_bf16) round every weight of the
+                                    3x3 conv, fc6 and fc7 once to the nearest bf16, ties to even, as loading a bf16 checkpoint would; the LI heads'
+                                    packed operand is fed the rounded values.  Spikes are {0, 1}, so products stay exact; accumulation and neuron
+                                    state stay fp32.  The result is the fp32 computation on the ROUNDED weights - like SNN_PRECISION_MXFP6 this
+                                    mode is OUTSIDE the 1e-4-to-the-fp32-reference contract.  A third of the matrix instructions and weight bytes
+                                    of the conv + LIF, fc6 and fc7 launches.  Not a default; nothing falls back to it or from it */
+
 typedef struct snn_rpn_level {
     const float* feat;     /* [N][C][H][W] fp32, NCHW contiguous (what the FPN hands over) */
     int32_t N, H, W;
@@ -346,6 +353,20 @@ size_t snn_packed_conv3x3_bf16x3_elems(int C_out, int C_in);
 int snn_pack_conv3x3_weight_bf16x3(const float* w_oihw, int C_out, int C_in, uint16_t* packed, snn_stream_t s);
 size_t snn_packed_linear_bf16x3_elems(int N, int K);
 int snn_pack_linear_weight_bf16x3(const float* w_nk, int N, int K, uint16_t* packed, snn_stream_t s);
+/* Single bf16 plane (SNN_PRECISION_BF16): uint16 [K/32][Np][32], each element the bf16 nearest to the fp32 weight (ties to even, subnormal results
+ * kept: bit for bit torch's w.to(torch.bfloat16)) - the *_elems counts are a third of the bf16x3 ones.  The _perm form packs fc6 in bin-major order
+ * as snn_pack_linear_weight_bf16x3_perm does.  A tensor with a non-finite weight or one that rounds to +-inf is REFUSED: the call returns -4
+ * (snn_last_error) - there is no other precision that computes the same thing to fall back to.  To deliver that verdict these three calls wait
+ * for the stream (pack time only).  Bad arguments return -1 before any device work.
+ * The LI heads have NO packer of their own at this precision: they keep snn_pack_heads_weight and its layout, and the CALLER rounds the two
+ * head weight matrices to bf16 (ties to even) and back to fp32 before that call, and refuses non-finite results itself - as the Python
+ * binding's ops.pack_heads_bf16 does.  Head weights passed unrounded run unrounded: the result is then not this mode's. */
+size_t snn_packed_bf16_elems(int K_chunks32, int N);
+size_t snn_packed_conv3x3_bf16_elems(int C_out, int C_in);
+int snn_pack_conv3x3_weight_bf16(const float* w_oihw, int C_out, int C_in, uint16_t* packed, snn_stream_t s);
+size_t snn_packed_linear_bf16_elems(int N, int K);
+int snn_pack_linear_weight_bf16(const float* w_nk, int N, int K, uint16_t* packed, snn_stream_t s);
+int snn_pack_linear_weight_bf16_perm(const float* w_nk, int N, int K, int inner, uint16_t* packed, snn_stream_t s);
 /* Block-scaled fp6 digit planes (precision "mxfp6", csrc/snn_mx.h): the fp32 weights as 6 planes of signed base-32
  * digits in fp6 e2m3 with one E8M0 scale per (32 consecutive k, column).  Exact for every weight within 2^5 of the
  * largest magnitude of its block, else rounded at 2^-28 of that magnitude.  Packed operand: uint32 words. */

@@ -12,7 +12,7 @@ c_stream = C.c_void_p
 
 SNN_MAX_LEVELS = 8
 SNN_MAX_STEPS = 32
-PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3}
+PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3, "bf16": 4}
 
 
 class snn_params(C.Structure):
@@ -108,6 +108,12 @@ SYMBOLS = {
     "snn_pack_conv3x3_weight_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "snn_packed_linear_bf16x3_elems": (C.c_size_t, [C.c_int, C.c_int]),
     "snn_pack_linear_weight_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "snn_packed_bf16_elems": (C.c_size_t, [C.c_int, C.c_int]),
+    "snn_packed_conv3x3_bf16_elems": (C.c_size_t, [C.c_int, C.c_int]),
+    "snn_pack_conv3x3_weight_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "snn_packed_linear_bf16_elems": (C.c_size_t, [C.c_int, C.c_int]),
+    "snn_pack_linear_weight_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "snn_pack_linear_weight_bf16_perm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "snn_check_bf16x3_split": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
     "snn_pack_linear_weight_bf16x3_perm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "snn_det_head_forward_k": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +

@@ -205,8 +205,12 @@ enum { G3_FC = 0, G3_CONV = 1, G3_CONV_LIF_REG = 2, G3_CONV_LIF_TILE = 3, G3_FC_
 // (Round 4 also ran fc6 + fc7 as ONE launch with per-row-tile counters and agent-scope release / acquire hand-offs between the two
 // layers' work-groups: bit-identical, 1 % slower - profiles/r4_det_pair.txt.  Removed in round 5: a measured negative, and its
 // bounded-wait failure path could only trap.)
-template <int MODE, int NB, int MT, int WN>
+// NPL = bf16 planes of the packed weights: 3 (hi + mid + lo: exact) or 1 (precision "bf16": the packer rounded every weight once to the nearest
+// bf16, snn_pack_*_bf16).  One plane: a chunk is 4 groups instead of 12 - each accumulator sees the hi plane's instructions in the same k
+// order -, the ring slots keep their size (same tiles, same occupancy).
+template <int MODE, int NB, int MT, int WN, int NPL = 3>
 __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const int bid) {
+    static_assert(NPL == 3 || NPL == 1, "weight planes");
     constexpr bool CONV = MODE == G3_CONV || MODE == G3_CONV_LIF_REG || MODE == G3_CONV_LIF_TILE;
     constexpr bool FUSE = MODE == G3_CONV_LIF_REG, TILE = MODE == G3_CONV_LIF_TILE || MODE == G3_FC_LIF_TILE;
     static_assert(((MT >= 2 && MT <= 4) || MT == 8) && (MT == 4 || !FUSE), "M-tiles per wave");
@@ -222,7 +226,8 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     constexpr int AW_BYTES = G3_AW_BYTES(WN);
     static_assert(NB == 3 || NB == 4, "ring depth");
     constexpr int SLOT = G3_SLOT(WN);
-    constexpr int PD = (CONV && !FUSE) ? 2 : 3, RING = PD + 1;  // 12 groups per chunk: RING must divide 12 (the 128-register conv
+    constexpr int NG = 4 * NPL;                                 // groups (one weight fragment, MT matrix instructions) per chunk
+    constexpr int PD = (CONV && !FUSE) ? (NPL == 3 ? 2 : 1) : 3, RING = PD + 1;  // 12 groups per chunk: RING must divide 12 (the 128-register conv
                                                                // rows have 128 registers: one fragment less in flight)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t smem_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
@@ -336,6 +341,7 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     const int cw_s = __builtin_amdgcn_readfirstlane(args.Cw);
     const uint32_t* f_ptr = static_cast<const uint32_t*>(sgpr_ptr(args.A - tap_back));
     uint32_t f_voff = CONV ? a_off - a_pitch : a_off;               // lane: row offset of tap row dy
+    static_assert(NG % RING == 0, "fragment ring carries over from chunk to chunk");
     int f_t = 0, f_kc = 0, f_j = 0, f_c = 0;
     const uint32_t a_dst = smem_base + G3_LUT_BYTES + wave * 256;   // + slot offset
     auto stage_a = [&](uint32_t slot_off) __attribute__((always_inline)) {
@@ -372,7 +378,7 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     // go round the 8 waves (piece p = wave, wave + 8, wave + 16: all of them on row block wave % (BN/16)).  Lane L
     // lands in physical unit L&3 of row (L>>2) of the piece, so it fetches logical unit (L&3) ^ swz(row): the swizzle
     // is applied on the SOURCE address, the LDS image stays lane-linear ----
-    constexpr int RBLK = BN / 16, NPIECE = 3 * RBLK;            // row blocks per plane, pieces per chunk (24 / 12)
+    constexpr int RBLK = BN / 16, NPIECE = NPL * RBLK;            // row blocks per plane, pieces per chunk (24 / 12)
     const int brow = (wave % RBLK) * 16 + (lane >> 2);
     const int bcol = min(nb * BN + brow, Np - 1);               // columns past Np: any valid row (never stored)
     const uint32_t b_off = (uint32_t)(bcol * 64 + (((lane & 3) ^ G3_SWZ(brow)) << 4));     // bytes within a chunk plane
@@ -385,7 +391,10 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     const uint32_t b_dst = smem_base + G3_LUT_BYTES + AW_BYTES + (wave % RBLK) * 1024;      // + slot offset, plane
     auto stage_next = [&](uint32_t slot_off) __attribute__((always_inline)) {
         const uint32_t d = __builtin_amdgcn_readfirstlane(b_dst + slot_off);                // wave-uniform LDS address
-        if (WN == 2) {
+        if constexpr (WN == 2 && NPL == 1) {
+            glds16(sgpr_ptr(reinterpret_cast<const void*>(s_ptr)), b_off, d);
+            if (NW == 4) glds16(sgpr_ptr(reinterpret_cast<const void*>(s_ptr)), b_off2, d + 4096);
+        } else if (WN == 2) {
             glds16x3(sgpr_ptr(reinterpret_cast<const void*>(s_ptr)), sgpr_ptr(reinterpret_cast<const void*>(s_ptr + b_plane)),
                      sgpr_ptr(reinterpret_cast<const void*>(s_ptr + 2 * b_plane)), b_off,
                      d, d + BN * G3_ROWB, d + 2 * BN * G3_ROWB);
@@ -426,7 +435,7 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     const unsigned char* const b_rd = ring + AW_BYTES + (wn * 64 + lr) * G3_ROWB + ((lg ^ G3_SWZ(lr)) << 4);
     // group g of a chunk = (N-tile g/3, plane 2 - g%3): per accumulator the small terms first (lo, mid, hi)
     auto rd_b = [&](uint32_t slot_off, int g) __attribute__((always_inline)) {
-        return *reinterpret_cast<const bf16x8*>(b_rd + slot_off + (2 - g % 3) * (BN * G3_ROWB) + (g / 3) * 16 * G3_ROWB);
+        return *reinterpret_cast<const bf16x8*>(b_rd + slot_off + (NPL - 1 - g % NPL) * (BN * G3_ROWB) + (g / NPL) * 16 * G3_ROWB);
     };
 
     // LIF state of the fused variant, whole T loop: v (64 registers) and the synaptic current i (48 registers;
@@ -545,15 +554,22 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
                 const uint32_t o_cur = (uint32_t)((u % NB) * SLOT), o_nxt = (uint32_t)(((u + 1) % NB) * SLOT),
                                o_wr = (uint32_t)(((u + NB - 1) % NB) * SLOT);
 #pragma unroll
-                for (int g = 0; g < 12; ++g) {
+                for (int g = 0; g < NG; ++g) {
                     const int gp = g + PD;
-                    bq[gp % RING] = gp < 12 ? rd_b(o_cur, gp) : rd_b(o_nxt, gp - 12);
-                    constexpr int AG0 = MT == 8 ? 4 : 8, WG0 = MT == 8 ? 0 : 4;      // groups that read the next chunk's A side
+                    bq[gp % RING] = gp < NG ? rd_b(o_cur, gp) : rd_b(o_nxt, gp - NG);
+                    constexpr int AG0 = NPL == 1 ? (MT == 8 ? 1 : 2) : MT == 8 ? 4 : 8, WG0 = (NPL == 1 || MT == 8) ? 0 : 4;      // groups that read the next chunk's A side
                     if (g == WG0) {
 #pragma unroll
                         for (int mt = 0; mt < MTA; ++mt) wq[mt] = rd_w(o_nxt, mt);
                     }
-                    if (g >= AG0 && g - AG0 < MTA) af[(u & 1) ^ 1][g - AG0] = rd_a(wq[g - AG0]);
+                    if constexpr (NPL == 3) {
+                        if (g >= AG0 && g - AG0 < MTA) af[(u & 1) ^ 1][g - AG0] = rd_a(wq[g - AG0]);
+                    } else {                                   // (four groups per chunk: the table fragments go out several per group)
+                        constexpr int PER = (MTA + NG - AG0 - 1) / (NG - AG0);
+#pragma unroll
+                        for (int i = 0; i < PER; ++i)
+                            if (g >= AG0 && (g - AG0) * PER + i < MTA) af[(u & 1) ^ 1][(g - AG0) * PER + i] = rd_a(wq[(g - AG0) * PER + i]);
+                    }
                     if (g == 2) {
                         stage_a(o_wr);
 #ifndef SNN_EXP_NO_GLDS
@@ -562,7 +578,7 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
                     }
 #pragma unroll
                     for (int mt = 0; mt < MTA; ++mt)
-                        acc[mt][g / 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u & 1][mt], bq[g % RING], acc[mt][g / 3], 0, 0, 0);
+                        acc[mt][g / NPL] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[u & 1][mt], bq[g % RING], acc[mt][g / NPL], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #ifndef SNN_EXP_NO_BARRIER
@@ -574,6 +590,10 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
                 // NB = 4: this chunk's own copies (the youngest vector-memory operations of the wave: its spike-word copy if it
                 // has rows to stage + 3 weight pieces, or 2 / 1 on the 8 x 1 wave grid) may stay in flight across the barrier
                 if (NB == 3) __builtin_amdgcn_s_waitcnt(0x0070);        // vmcnt(0) lgkmcnt(0)
+                else if constexpr (NPL == 1) {                          // (one plane: the spike-word copy + one weight piece, or none on waves 4 .. 7 of the 8 x 1 grid)
+                    const int own = (a_role ? 1 : 0) + ((WN == 2 || wave < NPIECE) ? 1 : 0);
+                    if (own == 2) __builtin_amdgcn_s_waitcnt(0x0072); else if (own == 1) __builtin_amdgcn_s_waitcnt(0x0071); else __builtin_amdgcn_s_waitcnt(0x0070);
+                }
                 else if (WN == 2) { if (a_role) __builtin_amdgcn_s_waitcnt(0x0074); else __builtin_amdgcn_s_waitcnt(0x0073); }
                 else if (wave + 8 < NPIECE) { if (a_role) __builtin_amdgcn_s_waitcnt(0x0073); else __builtin_amdgcn_s_waitcnt(0x0072); }
                 else { if (a_role) __builtin_amdgcn_s_waitcnt(0x0072); else __builtin_amdgcn_s_waitcnt(0x0071); }
@@ -909,6 +929,11 @@ template <int MODE, int NB, int MT, int WN>
 __global__ __launch_bounds__(MT == 8 ? 256 : 512, (MODE == G3_CONV_LIF_REG || MT == 8) ? 2 : 4) void k_gemm_bf16x3(const Gemm3Args args) {
     gemm_bf16x3_body<MODE, NB, MT, WN>(args, (int)blockIdx.x);
 }
+// precision "bf16": the same modes and tiles on ONE weight plane [Kc][Np][32]
+template <int MODE, int NB, int MT, int WN>
+__global__ __launch_bounds__(MT == 8 ? 256 : 512, (MODE == G3_CONV_LIF_REG || MT == 8) ? 2 : 4) void k_gemm_bf16(const Gemm3Args args) {
+    gemm_bf16x3_body<MODE, NB, MT, WN, 1>(args, (int)blockIdx.x);
+}
 
 // fp32 weights -> three bf16 planes [3][Kc][Np][32]  (hi = rn(w), mid = rn(w - hi), lo = rn(w - hi - mid): exact)
 __device__ __forceinline__ uint16_t f2bf_rn(float f) {
@@ -972,4 +997,35 @@ __global__ void k_pack_bf16x3(const float* __restrict__ src, uint16_t* __restric
         const uint16_t lo = f2bf_rn(r2);
         dst[idx] = hi; dst[plane + idx] = mid; dst[2 * plane + idx] = lo;
     }
+}
+
+// precision "bf16": ONE plane [Kc][Np][32] - every weight rounded once to the nearest bf16, ties to even: bit for bit what w.to(torch.bfloat16)
+// gives, subnormal results included (f2bf_rn's integer rounding is exact for every finite input).  status[0] += weights that are not finite or
+// round to +-inf: the pack call then fails - the mode has no other precision to fall back to that computes the same thing.
+__global__ void k_pack_bf16(const float* __restrict__ src, uint16_t* __restrict__ dst, int mode, int K, int N,
+                            int Kc, int Np, int Cin, int Cp, uint32_t* __restrict__ status) {
+    const size_t plane = (size_t)Kc * Np * 32;
+    uint32_t bad = 0;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < plane; idx += (size_t)gridDim.x * blockDim.x) {
+        const int kk = idx & 31;
+        const size_t rest = idx >> 5;
+        const int n = (int)(rest % Np);
+        const int kc = (int)(rest / Np);
+        const int k = kc * 32 + kk;
+        float w = 0.0f;
+        if (n < N) {
+            if (mode == PACK_CONV3X3) {
+                const int tap = k / Cp, ci = k % Cp;
+                if (ci < Cin) w = src[((size_t)n * Cin + ci) * 9 + tap];
+            } else if (mode == PACK_LINEAR_PERM) {         // (as k_pack_bf16x3: k' = s * Cp + c  <-  source column c * Cin + s)
+                if (k < K) w = src[(size_t)n * K + (size_t)(k % Cp) * Cin + k / Cp];
+            } else if (k < K) {
+                w = src[(size_t)n * K + k];
+            }
+        }
+        const uint16_t hi = f2bf_rn(w);
+        if ((__float_as_uint(w) & 0x7f800000u) == 0x7f800000u || (hi & 0x7f80u) == 0x7f80u) ++bad;
+        dst[idx] = hi;
+    }
+    if (bad) atomicAdd(status, bad);
 }

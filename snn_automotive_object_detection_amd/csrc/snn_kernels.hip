@@ -57,8 +57,20 @@ static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // SNN_PRECISION_F32_STRICT = the fp32 family with the LI heads on the fp32 VALU kernel as well: no weight is ever split into bf16 planes
-static inline int prec_family(int precision) { return precision == SNN_PRECISION_F32_STRICT ? SNN_PRECISION_F32 : precision; }
+// SNN_PRECISION_BF16 = the bf16x3 family - same encoders, planes, launch plans, LI heads - on ONE weight plane (the packers rounded every weight to
+// the nearest bf16): its contractions run the single-plane kernels k_gemm_lif_sparse1 / k_gemm_bf16
+static inline int prec_family(int precision) {
+    return precision == SNN_PRECISION_F32_STRICT ? SNN_PRECISION_F32 : precision == SNN_PRECISION_BF16 ? SNN_PRECISION_BF16X3 : precision;
+}
 static inline int prec_family(const snn_params* p) { return prec_family(p->precision); }
+// weight planes of the bf16 matrix-core launches enqueued by this thread: 3, or 1 inside a head forward at SNN_PRECISION_BF16 (the stage-level
+// entry points always run three)
+static thread_local int g_weight_planes = 3;
+struct WeightPlanesScope {
+    int prev;
+    explicit WeightPlanesScope(const snn_params* p) : prev(g_weight_planes) { g_weight_planes = (p && p->precision == SNN_PRECISION_BF16) ? 1 : 3; }
+    ~WeightPlanesScope() { g_weight_planes = prev; }
+};
 
 static NeuronP make_p(const snn_params* p, float v_th) {
     NeuronP q;
@@ -399,6 +411,14 @@ static int g3_bm(int wn, int mt) { return mt == 8 ? 256 : G3_BM(wn, mt); }
 
 template <int MODE>
 static const void* g3_kernel(int mt, int wn) {
+    if (g_weight_planes == 1) {
+        if (wn == 2)
+            return mt == 8 ? (const void*)k_gemm_bf16<MODE, 3, 8, 2>
+                 : mt == 4 ? (const void*)k_gemm_bf16<MODE, 3, 4, 2> : mt == 3 ? (const void*)k_gemm_bf16<MODE, 3, 3, 2>
+                                                                                : (const void*)k_gemm_bf16<MODE, 3, 2, 2>;
+        return mt == 4 ? (const void*)k_gemm_bf16<MODE, G3_NB1, 4, 1> : mt == 3 ? (const void*)k_gemm_bf16<MODE, G3_NB1, 3, 1>
+                                                                                  : (const void*)k_gemm_bf16<MODE, G3_NB1, 2, 1>;
+    }
     if (wn == 2)
         return mt == 8 ? (const void*)k_gemm_bf16x3<MODE, 3, 8, 2>
              : mt == 4 ? (const void*)k_gemm_bf16x3<MODE, 3, 4, 2> : mt == 3 ? (const void*)k_gemm_bf16x3<MODE, 3, 3, 2>
@@ -578,6 +598,47 @@ int snn_pack_linear_weight_bf16x3_perm(const float* w, int N, int K, int inner, 
     return 0;
 }
 
+// ---- bf16 (precision "bf16"): ONE plane, every weight rounded once to the nearest bf16 -----------------------------------------------
+size_t snn_packed_bf16_elems(int K_chunks32, int N) { return (size_t)K_chunks32 * (cdiv(N, 32) * 32) * 32; }
+size_t snn_packed_conv3x3_bf16_elems(int C_out, int C_in) { return snn_packed_bf16_elems(9 * cdiv(C_in, 32), C_out); }
+size_t snn_packed_linear_bf16_elems(int N, int K) { return snn_packed_bf16_elems(cdiv(K, 32), N); }
+
+// the pack launch + its verdict: the call waits for the stream and fails if a weight was not finite or rounded to +-inf
+static int pack_bf16_launch(const char* who, const float* w, uint16_t* packed, int mode, int K, int N, int Kc, int Np, int Cin, int Cp, snn_stream_t s) {
+    const size_t total = (size_t)Kc * Np * 32;
+    uint32_t* status = nullptr;
+    if (hipMalloc((void**)&status, sizeof(uint32_t)) != hipSuccess) return fail(-3, "%s: hipMalloc failed", who);
+    uint32_t bad = 0;
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t), (hipStream_t)s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_pack_bf16, dim3((unsigned)min((size_t)4096, (total + 255) / 256)), dim3(256), 0, (hipStream_t)s, w, packed, mode, K, N, Kc, Np,
+                           Cin, Cp, status);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, status, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)s);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)s);
+    (void)hipFree(status);
+    if (e != hipSuccess) return fail(-3, "%s: %s", who, hipGetErrorString(e));
+    if (bad) return fail(-4, "%s: %u weight(s) are not finite or round to +-inf in bf16 (precision \"bf16\" has no other precision to fall back to)", who, bad);
+    return 0;
+}
+
+int snn_pack_conv3x3_weight_bf16(const float* w, int C_out, int C_in, uint16_t* packed, snn_stream_t s) {
+    if (!w || !packed || C_out <= 0 || C_in <= 0) return fail(-1, "snn_pack_conv3x3_weight_bf16: bad argument");
+    const int Cp = cdiv(C_in, 32) * 32, Kc = 9 * (Cp / 32), Np = cdiv(C_out, 32) * 32;
+    return pack_bf16_launch("snn_pack_conv3x3_weight_bf16", w, packed, (int)PACK_CONV3X3, 9 * Cp, C_out, Kc, Np, C_in, Cp, s);
+}
+
+int snn_pack_linear_weight_bf16(const float* w, int N, int K, uint16_t* packed, snn_stream_t s) {
+    if (!w || !packed || N <= 0 || K <= 0) return fail(-1, "snn_pack_linear_weight_bf16: bad argument");
+    return pack_bf16_launch("snn_pack_linear_weight_bf16", w, packed, (int)PACK_LINEAR, K, N, cdiv(K, 32), cdiv(N, 32) * 32, 0, 32, s);
+}
+
+int snn_pack_linear_weight_bf16_perm(const float* w, int N, int K, int inner, uint16_t* packed, snn_stream_t s) {
+    if (!w || !packed || N <= 0 || K <= 0 || inner <= 0 || K % inner) return fail(-1, "snn_pack_linear_weight_bf16_perm: bad argument");
+    return pack_bf16_launch("snn_pack_linear_weight_bf16_perm", w, packed, (int)PACK_LINEAR_PERM, K, N, cdiv(K, 32), cdiv(N, 32) * 32, inner, K / inner, s);
+}
+
 // ---- block-scaled fp6 digit planes (snn_mx.h) ---------------------------------------------------
 size_t snn_packed_linear_mx_words(int N, int K) { return mx_words(cdiv(K, 128), cdiv(N, 32) * 32); }
 size_t snn_packed_conv3x3_mx_words(int C_out, int C_in) { return mx_words(9 * cdiv(C_in, 128), cdiv(C_out, 32) * 32); }
@@ -621,7 +682,7 @@ static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, G3Launch*
     switch (mode) {
     case G3_FC: kern = g3_kernel<G3_FC>(mt, wn); break;
     case G3_CONV: kern = g3_kernel<G3_CONV>(mt, wn); break;
-    case G3_CONV_LIF_REG: kern = (const void*)k_gemm_bf16x3<G3_CONV_LIF_REG, 3, 4, 2>; lds = G3_LDS(3, 2) + G3_STATE_BYTES; break;
+    case G3_CONV_LIF_REG: kern = g_weight_planes == 1 ? (const void*)k_gemm_bf16<G3_CONV_LIF_REG, 3, 4, 2> : (const void*)k_gemm_bf16x3<G3_CONV_LIF_REG, 3, 4, 2>; lds = G3_LDS(3, 2) + G3_STATE_BYTES; break;
     case G3_CONV_LIF_TILE: kern = g3_kernel<G3_CONV_LIF_TILE>(mt, wn); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
     default: kern = g3_kernel<G3_FC_LIF_TILE>(mt, wn); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
     }
@@ -633,7 +694,7 @@ static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, G3Launch*
     ax.n_tiles = tiles; ax.xcd_classes = 0;
     ax.epi_general = knobs().epi_general;
     int grid = tiles * a.n_blocks;
-    const size_t pair_bytes = (size_t)2 * G3_BN(wn) * a.Kc * 32 * 2 * 3;
+    const size_t pair_bytes = (size_t)2 * G3_BN(wn) * a.Kc * 32 * 2 * g_weight_planes;
     const bool conv_mode = mode == G3_CONV || mode == G3_CONV_LIF_TILE;
     if (knobs().bf16x3_xcd && mt != 8 && conv_mode && (a.n_blocks == 2 || (a.n_blocks == 4 && pair_bytes <= (size_t)2 << 20)) && tiles >= 64) {
         // 3x3 convolution with two / four column blocks: half of them and a contiguous quarter of the row tiles per XCD (halo rows stay
@@ -1107,6 +1168,9 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     if (mode == SPARSE_QUERY) return 1;
     const void* kern = sp.fat ? (conv ? (sp.wn == 1 ? (const void*)k_gemm_lif_sparse<true, 1, true> : (const void*)k_gemm_lif_sparse<true, 2, true>) : (const void*)k_gemm_lif_sparse<false, 2, true>)
                               : conv ? (const void*)k_gemm_lif_sparse<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse<false, 2> : (const void*)k_gemm_lif_sparse<false, 1>;
+    if (g_weight_planes == 1)
+        kern = sp.fat ? (conv ? (sp.wn == 1 ? (const void*)k_gemm_lif_sparse1<true, 1, true> : (const void*)k_gemm_lif_sparse1<true, 2, true>) : (const void*)k_gemm_lif_sparse1<false, 2, true>)
+                      : conv ? (const void*)k_gemm_lif_sparse1<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse1<false, 2> : (const void*)k_gemm_lif_sparse1<false, 1>;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, sh.lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     if (mode != SPARSE_RUN_COMPRESSED) {
@@ -1149,7 +1213,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     // round 6: the FAT conv on 4 x 1 waves (T = 7 .. 9, LIF in registers) in its ping-pong form - one persistent work-group of 8 waves per CU
     // (snn_sparse_pp.h); same plan, same arguments, bit-identical planes
     const int pp_ns = a.Tc - sp.nd;
-    if (conv && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
+    if (g_weight_planes == 3 && conv && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
         const void* kpp = pp_ns == 4 ? (const void*)k_conv_lif_pp<4> : (const void*)k_conv_lif_pp<5>;
         e = hipFuncSetAttribute(kpp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -1806,7 +1870,7 @@ size_t snn_rpn_head_workspace_bytes(const snn_rpn_level* lv, int n_levels, int C
     if (!lv || n_levels <= 0 || n_levels > SNN_MAX_LEVELS || C <= 0 || T < 1) return 0;
     size_t a, b, c, tot;
     rpn_ws_layout(rpn_positions(lv, n_levels, nullptr), prec_family(precision) != SNN_PRECISION_F32 ? rpn_positions_padded(lv, n_levels) : 0,
-                  C, T, precision, &a, &b, &c, &tot);
+                  C, T, precision == SNN_PRECISION_BF16 ? (int)SNN_PRECISION_BF16X3 : precision, &a, &b, &c, &tot);
     return tot;
 }
 
@@ -1827,6 +1891,7 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
     if (prec_family(p) == SNN_PRECISION_MXFP6 && (C % 128 || !mx_tile_ok(lif_window_full_out(T).n)))
         return fail(-4, "snn_rpn_head_forward: the mxfp6 kernels need C %% 128 == 0 and a T that fits a 512-row tile (C=%d, T=%d)", C, T);
     if (check_T(T, "snn_rpn_head_forward")) return -1;
+    const WeightPlanesScope planes(p);
     for (int l = 0; l < n_levels; ++l)
         if (!lv[l].feat || lv[l].N <= 0 || lv[l].H <= 0 || lv[l].W <= 0)
             return fail(-1, "snn_rpn_head_forward: bad level %d", l);
@@ -2322,6 +2387,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
     // folded (round 5): the encoder launch already wrote the planes in fc6's permuted order, e_3 .. compressed (k_encode_rows_perm): no
     // k_permute_planes, no k_compress_planes - fc6 must then run the structured-sparse launch (it was asked beforehand)
     const size_t o_enc = dp.o_enc, o_cur = dp.o_cur, o_s6 = dp.o_s6, o_s7 = dp.o_s7;
+    const WeightPlanesScope planes(p);
     const DetWindows& win = dp.win;
     const bool enc_wm = dp.wm, enc_periods = dp.per;
     hipStream_t s = (hipStream_t)stream;

@@ -36,7 +36,8 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         self.p_lif = ops.LIFParameters(alpha=100, v_th=torch.tensor(0.1))   # :449,452
         self.li_order = "jump_first"
         self.spike_rates = False
-        self.precision = "bf16x3"          # or "f32" (fp32 matrix cores) / "mxfp6" (fp4 x fp6 digit planes); see RPNHeadSNN
+        self.precision = "bf16x3"          # or "f32" (fp32 matrix cores) / "mxfp6" (fp4 x fp6 digit planes) / "bf16" (ONE bf16 weight plane: fc6, fc7
+                                           # and the LI heads on w.to(torch.bfloat16) - outside the 1e-4-to-fp32 contract, as "mxfp6"); see RPNHeadSNN
         self.fc6 = nn.Linear(in_channels, representation_size, bias=False)          # :448
         self.fc7 = nn.Linear(representation_size, representation_size, bias=False)  # :451
         self.cls_score = nn.Linear(representation_size, num_classes, bias=False)    # :455
@@ -46,11 +47,15 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         self._c7 = _per_precision()
         self._ch = _WeightCache()
         self._c6p = _WeightCache()              # fc6 in the permuted reduction order (fc6_inner)
+        self._ch_bf16 = _WeightCache()          # "bf16": the LI heads' operand packed from the rounded values
+        self._c6p_bf16 = _WeightCache()         # "bf16": fc6's single plane in the permuted order
 
     def _caches(self):
-        return list(self._c6.values()) + list(self._c7.values()) + [self._ch, self._c6p]
+        return list(self._c6.values()) + list(self._c7.values()) + [self._ch, self._c6p, self._ch_bf16, self._c6p_bf16]
 
     def _split_weights(self, prec):
+        if prec == "bf16":
+            return ()
         return (self.cls_score.weight, self.bbox_pred.weight) + ((self.fc6.weight, self.fc7.weight) if prec == "bf16x3" else ())
 
     def _eff_precision(self) -> str:
@@ -65,7 +70,7 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         prec = prec or self._resolve_precision()
         # (mirrors the C side's gates: the permuted order needs the word-major fused bf16x3 layers - SNN_PLANES=rm, an A/B knob, switches
         # them off; any channel count that is a multiple of 32 is fine since round 5: k_permute_planes works in passes of 8 channel blocks)
-        if prec != "bf16x3" or os.environ.get("SNN_FC6_PERM") == "0" or os.environ.get("SNN_PLANES") == "rm":
+        if prec not in ("bf16x3", "bf16") or os.environ.get("SNN_FC6_PERM") == "0" or os.environ.get("SNN_PLANES") == "rm":
             return 0
         return 49 if (self.in_channels % 49 == 0 and (self.in_channels // 49) % 32 == 0) else 0
 
@@ -74,15 +79,20 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         reference's reduction order whatever fc6_inner() says (the stage-level ops read un-permuted planes)"""
         prec = prec or self._resolve_precision()
         pack = {"f32": ops.pack_linear, "f32_strict": ops.pack_linear, "bf16x3": lambda w: ops.pack_linear_bf16x3(w, check_split=False),
-                "mxfp6": ops.pack_linear_mx}[prec]
+                "mxfp6": ops.pack_linear_mx, "bf16": ops.pack_linear_bf16}[prec]
         slot = "f32" if prec == "f32_strict" else prec
         inner = self.fc6_inner(prec) if inner is None else inner
-        if inner:
+        if inner and prec == "bf16":
+            w6 = self._c6p_bf16.get((self.fc6.weight,), lambda w: ops.pack_linear_bf16(w, inner=inner))
+        elif inner:
             w6 = self._c6p.get((self.fc6.weight,), lambda w: ops.pack_linear_bf16x3(w, check_split=False, inner=inner))
         else:
             w6 = self._c6[slot].get((self.fc6.weight,), pack)
         w7 = self._c7[slot].get((self.fc7.weight,), pack)
-        wh = self._ch.get((self.cls_score.weight, self.bbox_pred.weight), _pack_heads_unchecked)
+        if prec == "bf16":
+            wh = self._ch_bf16.get((self.cls_score.weight, self.bbox_pred.weight), ops.pack_heads_bf16)
+        else:
+            wh = self._ch.get((self.cls_score.weight, self.bbox_pred.weight), _pack_heads_unchecked)
         return w6, w7, wh
 
     def _pass_args(self, width: int, got: str) -> dict:

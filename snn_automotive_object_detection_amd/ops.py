@@ -172,6 +172,51 @@ def pack_linear_bf16x3(w: torch.Tensor, check_split: bool = True, inner: int = 0
     return out
 
 
+def round_bf16(w: torch.Tensor) -> torch.Tensor:
+    """the fp32 values precision "bf16" computes with: each weight rounded once to the nearest bf16, ties to even"""
+    return w.detach().to(torch.bfloat16).to(torch.float32)
+
+
+def pack_heads_bf16(wa: torch.Tensor, wb: torch.Tensor) -> torch.Tensor:
+    """the LI heads' packed operand for precision "bf16": the heads keep their kernels and layout and are fed the ROUNDED values
+    (the mid and lo planes the kernels split off are then zero; rounded values always split exactly).  Raises SnnHipError on a weight
+    that is not finite or rounds to +-inf (one host synchronisation per weight update)"""
+    _need_gpu(wa, "head weight")
+    ra, rb = round_bf16(_f32c(wa)), round_bf16(_f32c(wb))
+    bad = int((~torch.isfinite(ra)).sum()) + int((~torch.isfinite(rb)).sum())
+    if bad:
+        raise _lib.SnnHipError("pack_heads_bf16: %d LI head weight(s) are not finite or round to +-inf in bf16 "
+                               "(precision \"bf16\" has no other precision to fall back to)" % bad)
+    return pack_heads(ra, rb, check_split=False)
+
+
+def pack_conv3x3_bf16(w: torch.Tensor) -> torch.Tensor:
+    """ONE bf16 plane [K/32][Np][32] (precision "bf16"): bit for bit ``w.to(torch.bfloat16)``.  Raises SnnHipError if a weight is not
+    finite or rounds to +-inf (one host synchronisation - weights are packed when they change, not per forward)"""
+    _need_gpu(w, "conv weight")
+    lib = _lib.load()
+    w = _f32c(w)
+    co, ci = w.shape[0], w.shape[1]
+    out = torch.empty(lib.snn_packed_conv3x3_bf16_elems(co, ci), dtype=torch.int16, device=w.device)
+    _lib.check(lib.snn_pack_conv3x3_weight_bf16(_ptr(w), co, ci, _ptr(out), _stream()), "snn_pack_conv3x3_weight_bf16")
+    return out
+
+
+def pack_linear_bf16(w: torch.Tensor, inner: int = 0) -> torch.Tensor:
+    """ONE bf16 plane (precision "bf16"); ``inner`` as in pack_linear_bf16x3.  Raises SnnHipError on a weight that is not finite or
+    rounds to +-inf"""
+    _need_gpu(w, "linear weight")
+    lib = _lib.load()
+    w = _f32c(w)
+    n, k = w.shape
+    out = torch.empty(lib.snn_packed_linear_bf16_elems(n, k), dtype=torch.int16, device=w.device)
+    if inner > 1:
+        _lib.check(lib.snn_pack_linear_weight_bf16_perm(_ptr(w), n, k, int(inner), _ptr(out), _stream()), "snn_pack_linear_weight_bf16_perm")
+    else:
+        _lib.check(lib.snn_pack_linear_weight_bf16(_ptr(w), n, k, _ptr(out), _stream()), "snn_pack_linear_weight_bf16")
+    return out
+
+
 def pack_linear_mx(w: torch.Tensor) -> torch.Tensor:
     """[N, K] fp32 -> block-scaled fp6 digit planes (int32 words, csrc/snn_mx.h)"""
     _need_gpu(w, "weight")
@@ -875,7 +920,7 @@ def _on_tensor_device(fn):
     return guarded
 
 
-for _name in ("pack_conv3x3", "pack_linear", "pack_heads", "pack_conv3x3_bf16x3", "pack_linear_bf16x3", "pack_linear_mx",
+for _name in ("pack_conv3x3", "pack_linear", "pack_heads", "pack_conv3x3_bf16x3", "pack_linear_bf16x3", "pack_conv3x3_bf16", "pack_linear_bf16", "pack_heads_bf16", "pack_linear_mx",
               "pack_conv3x3_mx", "spike_gemm_bf16x3", "spike_gemm_lif_bf16x3", "spike_gemm_mx", "spike_gemm_lif_mx",
               "conv3x3_lif_mx", "spike_conv3x3_mx", "conv3x3_lif_bf16x3", "spike_conv3x3_bf16x3", "affine_act_nchw", "encode_nchw", "encode_rows",
               "conv3x3_lif", "spike_gemm", "lif_scan", "det_exchange_payload", "li_heads", "rpn_head_forward", "det_head_forward",

@@ -63,7 +63,7 @@ def _strict_if_inexact(module, prec: str, box) -> str:
 
 def _per_precision():
     """one packed-weight cache per packing ("f32_strict" packs as "f32")"""
-    return {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache()}
+    return {"f32": _WeightCache(), "bf16x3": _WeightCache(), "mxfp6": _WeightCache(), "bf16": _WeightCache()}
 
 
 class _SpikingHead(nn.Module):
@@ -103,6 +103,8 @@ class _SpikingHead(nn.Module):
         if prec == "f32_strict":
             return prec
         split = self._split_weights(prec)
+        if not split:                                                 # ("bf16": every operand is packed from rounded values, which always split exactly;
+            return prec                                               # a weight that cannot be rounded makes the packers raise - no fallback)
         if not split[0].is_cuda:                                      # (CPU weights: forward raises anyway - no CPU path)
             return prec
         return _strict_if_inexact(self, prec, self._cache_split.get(split, _warn_once_box(ops.split_problem)))
@@ -136,6 +138,11 @@ class RPNHeadSNN(_SpikingHead):
         # "mxfp6": fp4 x fp6 block-scaled matrix path, weights as 6 planes of base-32 digits (exact within 2^5 of the
         #          block maximum, else rounded at 2^-28 of it; ~1.4x faster); needs in_channels % 128 == 0, otherwise
         #          the bf16x3 kernels run.
+        # "bf16": the bf16x3 path on ONE bf16 weight plane - every weight of the 3x3 conv and the two 1x1 heads is rounded once to the
+        #          nearest bf16 (ties to even, in the packers: parameters and state_dict stay fp32), as loading a bf16 checkpoint would;
+        #          spikes are {0, 1}, so products stay exact, accumulation and neuron state stay fp32.  The result is the fp32
+        #          computation on w.to(torch.bfloat16).float() - like "mxfp6" OUTSIDE the 1e-4-to-the-fp32-reference contract.  A third
+        #          of the conv's matrix instructions and weight bytes.  Any channel count; non-finite weights raise (no fallback).
         self.precision = "bf16x3"
         # parameters: identical modules so that state_dict keys/shapes match the reference
         self.shared_conv = nn.Conv2d(in_channels, in_channels, kernel_size=(3, 3), stride=(1, 1),
@@ -147,11 +154,14 @@ class RPNHeadSNN(_SpikingHead):
                 torch.nn.init.normal_(layer.weight, std=0.01)
         self._cache_shared = _per_precision()
         self._cache_heads = _WeightCache()
+        self._cache_heads_bf16 = _WeightCache()  # the LI heads' operand packed from the rounded values ("bf16")
 
     def _caches(self):
-        return list(self._cache_shared.values()) + [self._cache_heads]
+        return list(self._cache_shared.values()) + [self._cache_heads, self._cache_heads_bf16]
 
     def _split_weights(self, prec):
+        if prec == "bf16":
+            return ()
         return (self.conv_cls.weight, self.conv_bbox.weight) + ((self.shared_conv.weight,) if prec == "bf16x3" else ())
 
     def _eff_precision(self) -> str:
@@ -162,14 +172,17 @@ class RPNHeadSNN(_SpikingHead):
     def _packed_shared(self, prec=None):
         prec = prec or self._resolve_precision()
         pack = {"f32": ops.pack_conv3x3, "f32_strict": ops.pack_conv3x3, "bf16x3": lambda w: ops.pack_conv3x3_bf16x3(w, check_split=False),
-                "mxfp6": ops.pack_conv3x3_mx}[prec]
+                "mxfp6": ops.pack_conv3x3_mx, "bf16": ops.pack_conv3x3_bf16}[prec]
         return self._cache_shared["f32" if prec == "f32_strict" else prec].get((self.shared_conv.weight,), pack)
 
     def _pass_args(self):
         """(C, A, parameters, packed shared conv, packed LI heads) of one head pass"""
         prec = self._resolve_precision()
         w_shared = self._packed_shared(prec)
-        w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
+        if prec == "bf16":
+            w_heads = self._cache_heads_bf16.get((self.conv_cls.weight, self.conv_bbox.weight), ops.pack_heads_bf16)
+        else:
+            w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
         return self.in_channels, self.num_anchors, self._params(prec), w_shared, w_heads
 
     def _level_views(self, x, out_l, out_b, rows, rate_rows):

@@ -1,0 +1,629 @@
+"""Precision "bf16" on the GPU: ONE bf16 weight plane through both spiking heads.
+
+The contract: a head at precision "bf16" with weights w computes what the fp32 paths compute on w.to(torch.bfloat16).float() - the
+packers round, nothing else changes.  The single-plane kernels give every accumulator the three-plane kernels' instructions in the same
+k order minus those of the mid / lo planes, so on bf16-representable weights both give the SAME BITS: head(w, "bf16") is compared with
+torch.equal against head(round(w), "bf16x3") - outputs, spike counts / rates and the hidden spike planes in the workspace - over a grid
+that reaches every launch family.  Against the oracle run on the rounded weights: the sentinel neurons of tests/_sentinels.py, the full-size
+cases of tests/test_gpu_fullsize.py (Cityscapes pyramid, 2000 RoIs, the stress configuration) and the golden fixtures - same tolerances, flip
+budgets (factor 1.0) and tie margin as bf16x3."""
+import ctypes as C
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+from tests._util import planes_to_dense, flip_budget
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+
+def _rnd(w):
+    return w.detach().to(torch.bfloat16).to(torch.float32)
+
+
+# ---- 1. the packers round like torch -----------------------------------------------------------------------------------------------
+def _bit_grid():
+    """fp32 bit patterns: the grid of test_pack_bf16x3_is_exact's kind (random bits over all exponents) + exact ties + values whose
+    rounded bf16 is subnormal + the largest values that still round to a finite bf16"""
+    g = torch.Generator().manual_seed(7)
+    bits = torch.randint(0, 2 ** 31 - 1, (16384,), generator=g, dtype=torch.int64)
+    bits = bits | (torch.randint(0, 2, (16384,), generator=g, dtype=torch.int64) << 31)
+    vals = bits.to(torch.int32).view(torch.float32)
+    vals = vals[torch.isfinite(vals) & (vals.abs() < 3.3e38)]
+    special = []
+    for hi in (0x3F80, 0x3F81, 0x0001, 0x0002, 0x007F, 0x0080, 0x7F00, 0x7F7E, 0x0000, 0xBF80, 0x8001):
+        for lo in (0x0000, 0x7FFF, 0x8000, 0x8001, 0xFFFF, 0x0001):          # below / exactly at / above the tie, both parities of hi
+            special.append((hi << 16) | lo)
+    special += [0x7F7F7FFF, 0xFF7F7FFF, 0x7F7F0000, 0x00000001, 0x00007FFF, 0x00008000, 0x00008001, 0x80008000]   # largest finite results, tiniest inputs
+    sp = torch.tensor([struct.unpack("<i", struct.pack("<I", b))[0] for b in special], dtype=torch.int32).view(torch.float32)
+    return torch.cat([sp, vals])                                   # (the special patterns first: every pack below sees them)
+
+
+def test_packers_round_like_torch(gpu_device):
+    from snn_automotive_object_detection_amd import ops
+    v = _bit_grid()
+    assert torch.isfinite(_rnd(v)).all() and v.numel() >= 33 * 40 * 9
+    assert int(((_rnd(v).view(torch.int32) & 0x7F800000) == 0).sum()) > 10       # subnormal (and zero) results are in the grid
+    # linear: [N, K] -> [K/32][Np][32]
+    N, K = 40, 98
+    w = v[: N * K].reshape(N, K).to(gpu_device)
+    ref = w.to(torch.bfloat16).view(torch.int16)
+    pk = ops.pack_linear_bf16(w).view(-1, 64, 32)                     # Kc = 4, Np = 64
+    Kc = pk.shape[0]
+    got = pk.permute(1, 0, 2).reshape(64, Kc * 32)
+    assert torch.equal(got[:N, :K], ref) and int(got[N:].ne(0).sum()) == 0 and int(got[:, K:].ne(0).sum()) == 0
+    # fc6's bin-major order: k' = s * C + c  <-  column c * inner + s
+    inner, Cc = 49, 2
+    pkp = ops.pack_linear_bf16(w, inner=inner).view(-1, 64, 32).permute(1, 0, 2).reshape(64, Kc * 32)
+    refp = ref.view(N, Cc, inner).permute(0, 2, 1).reshape(N, K)
+    assert torch.equal(pkp[:N, :K], refp)
+    # conv: OIHW [Co, Ci, 3, 3] -> k = tap * Cp + ci
+    Co, Ci = 33, 40
+    wc = v[: Co * Ci * 9].reshape(Co, Ci, 3, 3).to(gpu_device)
+    pc = ops.pack_conv3x3_bf16(wc).view(-1, 64, 32).permute(1, 0, 2).reshape(64, 9, 64)      # Cp = 64
+    refc = wc.to(torch.bfloat16).view(torch.int16).reshape(Co, Ci, 9).permute(0, 2, 1)
+    assert torch.equal(pc[:Co, :, :Ci], refc) and int(pc[:, :, Ci:].ne(0).sum()) == 0 and int(pc[Co:].ne(0).sum()) == 0
+    # the element counts are a third of the three-plane ones
+    assert ops.pack_linear_bf16(w).numel() * 3 == ops.pack_linear_bf16x3(_rnd(w)).numel()
+    # the single plane IS the three-plane packer's hi plane, and for rounded weights the other two planes are zero
+    p3 = ops.pack_linear_bf16x3(_rnd(w)).view(3, -1)
+    assert torch.equal(p3[0], ops.pack_linear_bf16(w).view(-1)) and int(p3[1:].ne(0).sum()) == 0
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf"), 3.4e38, -3.4e38])
+def test_packers_refuse_what_does_not_round_to_a_finite_bf16(gpu_device, bad):
+    from snn_automotive_object_detection_amd import ops, _lib
+    w = torch.randn(64, 98, device=gpu_device)
+    w[2, 5] = bad
+    for fn in (lambda: ops.pack_linear_bf16(w), lambda: ops.pack_linear_bf16(w, inner=49), lambda: ops.pack_conv3x3_bf16(w[:, :90].reshape(64, 10, 3, 3)),
+               lambda: ops.pack_heads_bf16(w[:3], w[3:15])):
+        with pytest.raises(_lib.SnnHipError, match="not finite or round"):
+            fn()
+    rc = _lib.load().snn_pack_linear_weight_bf16(C.c_void_p(w.data_ptr()), 64, 98, C.c_void_p(torch.empty(4 * 64 * 32, dtype=torch.int16, device=gpu_device).data_ptr()), None)
+    assert rc < 0 and b"snn_pack_linear_weight_bf16" in _lib.load().snn_last_error()
+    w[2, 5] = 3.38e38                                             # rounds to the largest finite bf16: accepted
+    ops.pack_linear_bf16(w)
+
+
+# ---- 3. bit identity to the three-plane path ----------------------------------------------------------------------------------------
+def _rpn_pair(pkg, dev, C_, A, T, seed):
+    g = torch.Generator().manual_seed(seed)
+    ws = torch.randn(C_, C_, 3, 3, generator=g) * 0.02
+    wc = torch.randn(A, C_, 1, 1, generator=g) * 0.05
+    wb = torch.randn(4 * A, C_, 1, 1, generator=g) * 0.05
+    heads = []
+    for prec, f in (("bf16", lambda t: t), ("bf16x3", _rnd)):
+        m = pkg.RPNHeadSNN(C_, A, T).to(dev)
+        m.precision = prec
+        m.load_state_dict({"shared_conv.weight": f(ws), "conv_cls.weight": f(wc), "conv_bbox.weight": f(wb)})
+        heads.append(m)
+    assert not torch.equal(ws, _rnd(ws))                            # the mode has something to round
+    return heads
+
+
+def _rpn_planes(dev, T, Cw):
+    from snn_automotive_object_detection_amd import _lib, ops
+    off3 = (C.c_uint64 * 3)()
+    _lib.load().snn_debug_last_rpn_planes(off3)
+    P = int(off3[2])
+    return ops._WS.get(dev, 1)[int(off3[0]): int(off3[0]) + T * P * Cw * 4].clone(), int(off3[1])
+
+
+def _det_planes(dev, T, Hd, R):
+    from snn_automotive_object_detection_amd import _lib, ops
+    off3 = (C.c_uint64 * 3)()
+    _lib.load().snn_debug_last_det_planes(off3)
+    n = T * (Hd // 32) * R * 4
+    ws = ops._WS.get(dev, 1)
+    return ws[int(off3[0]): int(off3[0]) + n].clone(), ws[int(off3[1]): int(off3[1]) + n].clone(), int(off3[2])
+
+
+RPN_SHAPES = [(37, 53), (19, 27), (7, 9)]
+
+
+@pytest.mark.parametrize("rates", [False, True])
+@pytest.mark.parametrize("C_,T", [(256, 4), (256, 5), (256, 8), (256, 9), (256, 12), (256, 16), (256, 20), (96, 8)])
+def test_rpn_head_equals_the_three_plane_path_on_rounded_weights(gpu_device, C_, T, rates):
+    """T = 4: dense conv tile; 5: 8-wave sparse; 8, 9: FAT 4 x 1; 12, 16: FAT 2 x 2; 20: dense tile, general epilogue; C = 96: dense
+    (C % 64 != 0).  spike_rates: the counting forms of the same launches"""
+    import snn_automotive_object_detection_amd as pkg
+    from snn_automotive_object_detection_amd import _lib
+    m1, m3 = _rpn_pair(pkg, gpu_device, C_, 3, T, 100 + T + C_)
+    g = torch.Generator().manual_seed(T)
+    feats = [(torch.randn(2, C_, h, w, generator=g) * 1.7).to(gpu_device) for h, w in RPN_SHAPES]
+    outs, planes, paths = [], [], []
+    for m in (m1, m3):
+        m.spike_rates = rates
+        o = m(feats)
+        outs.append([t.clone() for part in o for t in part] + ([m.last_spike_counts.clone()] if rates else []))
+        planes.append(_rpn_planes(gpu_device, T, (C_ + 31) // 32))
+        paths.append(_lib.load().snn_debug_last_conv_path())
+    assert paths[0] == paths[1]                                      # same launch family at both precisions
+    assert paths[0] == (1 if (C_ % 64 == 0 and 5 <= T <= 16) else 0), paths
+    assert planes[0][1] == planes[1][1] and torch.equal(planes[0][0], planes[1][0]), "hidden spike planes differ"
+    assert int(planes[0][0].view(torch.int32).ne(0).sum()) > 0
+    assert len(outs[0]) == len(outs[1])
+    for a, b in zip(outs[0], outs[1]):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("rates", [False, True])
+@pytest.mark.parametrize("T", [6, 8, 12, 14, 16, 24])
+def test_det_head_equals_the_three_plane_path_on_rounded_weights(gpu_device, T, rates):
+    """fc6 on the structured-sparse kernel (FAT 2 x 2 with the register LIF / tile image / general epilogue, counting mode) and fc7's
+    G3_FC_LIF_TILE; R = 300 leaves a partial tile"""
+    import snn_automotive_object_detection_amd as pkg
+    from snn_automotive_object_detection_amd import _lib
+    Cc, Hd, K, R = 64, 256, 9, 300
+    heads = _det_pair(pkg, gpu_device, Cc, Hd, K, T, 200 + T)
+    g = torch.Generator().manual_seed(T)
+    x = (torch.rand(R, Cc, 7, 7, generator=g) * 2.5).to(gpu_device)
+    outs, planes, paths = [], [], []
+    for m in heads:
+        m.spike_rates = rates
+        o = m(x)
+        outs.append([t.clone() for t in (o if isinstance(o, (tuple, list)) else [o])] + ([c.clone() for c in m.last_spike_counts] if rates else []))
+        planes.append(_det_planes(gpu_device, T, Hd, R))
+        paths.append(_lib.load().snn_debug_last_fc6_path())
+    assert paths[0] == paths[1], paths                               # same launch family at both precisions
+    assert T != 12 or paths[0] == 1, paths                           # ... the structured-sparse fc6 at the headline's T_det
+    assert planes[0][2] == planes[1][2]
+    assert torch.equal(planes[0][0], planes[1][0]) and torch.equal(planes[0][1], planes[1][1]), "hidden spike planes differ"
+    assert int(planes[0][0].view(torch.int32).ne(0).sum()) > 0 and int(planes[0][1].view(torch.int32).ne(0).sum()) > 0
+    for a, b in zip(outs[0], outs[1]):
+        assert torch.equal(a, b)
+
+
+def _det_pair(pkg, dev, Cc, Hd, K, T, seed):
+    g = torch.Generator().manual_seed(seed)
+    w6 = torch.randn(Hd, Cc * 49, generator=g) * 0.02
+    w7 = torch.randn(Hd, Hd, generator=g) * 0.05
+    wc = torch.randn(K, Hd, generator=g) * 0.05
+    wb = torch.randn(4 * K, Hd, generator=g) * 0.05
+    heads = []
+    for prec, f in (("bf16", lambda t: t), ("bf16x3", _rnd)):
+        m = pkg.FastRCNNPredictorSNNFull(Cc * 49, Hd, K, T).to(dev)
+        m.precision = prec
+        m.load_state_dict({"fc6.weight": f(w6), "fc7.weight": f(w7), "cls_score.weight": f(wc), "bbox_pred.weight": f(wb)})
+        heads.append(m)
+    return heads
+
+
+@pytest.mark.parametrize("T", [12, 24])
+def test_roialign_head_equals_the_three_plane_path_on_rounded_weights(gpu_device, T):
+    import snn_automotive_object_detection_amd as pkg
+    Cc, Hd, K, R = 64, 256, 9, 200
+    heads = _det_pair(pkg, gpu_device, Cc, Hd, K, T, 300 + T)
+    g = torch.Generator().manual_seed(T)
+    feats = [(torch.rand(2, Cc, 48 >> l, 64 >> l, generator=g) * 2.5).to(gpu_device) for l in range(3)]
+    scales = [0.25, 0.125, 0.0625]
+    xy = torch.rand(R, 2, generator=g) * torch.tensor([150.0, 100.0])
+    wh = torch.rand(R, 2, generator=g) * 80 + 8
+    rois = torch.cat([torch.randint(0, 2, (R, 1), generator=g).float(), xy, xy + wh], dim=1).to(gpu_device)
+    lvl = torch.randint(0, 3, (R,), generator=g).to(torch.int32).to(gpu_device)
+    outs, planes = [], []
+    for m in heads:
+        o = m.forward_roialign(feats, scales, rois, lvl)
+        outs.append([t.clone() for t in o])
+        planes.append(_det_planes(gpu_device, T, Hd, R))
+    assert torch.equal(planes[0][0], planes[1][0]) and torch.equal(planes[0][1], planes[1][1])
+    assert int(planes[0][1].view(torch.int32).ne(0).sum()) > 0
+    for a, b in zip(outs[0], outs[1]):
+        assert torch.equal(a, b)
+
+
+def test_readouts_equal_the_three_plane_path_on_rounded_weights(gpu_device):
+    import snn_automotive_object_detection_amd as pkg
+    m1, m3 = _rpn_pair(pkg, gpu_device, 256, 3, 12, 41)
+    g = torch.Generator().manual_seed(5)
+    feats = [(torch.randn(2, 256, h, w, generator=g) * 1.7).to(gpu_device) for h, w in RPN_SHAPES]
+    r1, r3 = m1.forward_readouts(feats, (4, 8, 12)), m3.forward_readouts(feats, (4, 8, 12))
+    for T in (4, 8, 12):
+        for a, b in zip(r1[T][0] + r1[T][1], r3[T][0] + r3[T][1]):
+            assert torch.equal(a, b), T
+    d1, d3 = _det_pair(pkg, gpu_device, 64, 256, 9, 16, 42)
+    x = (torch.rand(150, 64, 7, 7, generator=g) * 2.5).to(gpu_device)
+    q1, q3 = d1.forward_readouts(x, (6, 12, 16)), d3.forward_readouts(x, (6, 12, 16))
+    for T in (6, 12, 16):
+        for a, b in zip(q1[T], q3[T]):
+            assert torch.equal(a, b), T
+
+
+def _head_rpn_planes(dev, T, C_):
+    """the shared LIF's spike planes the last RPN forward left in the workspace, as rows [T, P, C / 32] (all levels, position-major)"""
+    from snn_automotive_object_detection_amd import _lib, ops
+    off3 = (C.c_uint64 * 3)()
+    _lib.load().snn_debug_last_rpn_planes(off3)
+    P, Cw = int(off3[2]), (C_ + 31) // 32
+    raw = ops._WS.get(dev, 1)[int(off3[0]): int(off3[0]) + T * P * Cw * 4].view(torch.int32)
+    return (raw.view(T, Cw // 4, P, 4).permute(0, 2, 1, 3).reshape(T, P, Cw) if off3[1] else raw.view(T, P, Cw)).contiguous().clone()
+
+
+def _head_det_planes(dev, T, Hd, R):
+    """lif6 / lif7 spike planes of the last detector forward as rows [T, R, Hd / 32]"""
+    p6, p7, wm = _det_planes(dev, T, Hd, R)
+    p6 = p6.view(torch.int32)
+    p6 = p6.view(T, Hd // 32, R).permute(0, 2, 1).contiguous() if wm else p6.view(T, R, Hd // 32)
+    return p6, p7.view(torch.int32).view(T, R, Hd // 32)
+
+
+# ---- 2. the mode really rounds: sentinel neurons -------------------------------------------------------------------------------------
+def _rpn_sentinel_prediction(case):
+    """tests/_sentinels.py's host prediction (proved equal to the oracle by tests/test_sentinels_cpu.py) for the ROUNDED weights: every
+    sentinel weight - hidden one-hot conv rows, head weights - replaced by its nearest bf16, trains and LI values recomputed"""
+    from tests import _sentinels as S
+    T, order = case["T"], case["li_order"]
+    kap = S.kappa64(T, order)
+    r = lambda v: float(S._bf16_rn(np.array([v], dtype=np.float32))[0])
+    exp, tol = [], []
+    changed = 0
+    for (H, W) in case["shapes"]:
+        e = np.zeros((case["N"], 5 * case["A"], H, W))
+        t_ = np.zeros_like(e)
+        for o, hd in enumerate(case["heads"]):
+            hs = case["hidden"][hd["hidden"]]
+            train = S.lif_train(r(hs["weight"]), S.period_sched(hs["period"], T))
+            u = r(hd["u"])
+            m = S._tap_inside(H, W, hs["tap"])
+            e[:, o] = np.where(m, S.li_last64(u, train, order)[0], 0.0)
+            t_[:, o] = np.where(m, S.head_tolerance(int(train.sum()), float(np.sum(kap[train])) * abs(u)), 0.0)
+            changed += int(u != hd["u"])
+        exp.append(e); tol.append(t_)
+    assert changed == 5 * case["A"] * len(case["shapes"])              # every head sentinel has non-zero mid / lo planes (design_head_weight)
+    return exp, tol
+
+
+@pytest.mark.parametrize("T", [5, 8, 12, 16])
+def test_rpn_sentinels_at_bf16(gpu_device, T):
+    """_sentinels weights (non-zero mid / lo planes, threshold-straddling pairs) through the module at "bf16": every sentinel output equals
+    the prediction for the ROUNDED weights within the sentinel bound, and is OFF the unrounded prediction that "bf16x3" meets"""
+    import snn_automotive_object_detection_amd as pkg
+    from snn_automotive_object_detection_amd import _lib
+    from tests import _sentinels as S
+    from tests._util import record_parity
+    case = S.rpn_case(256, 3, T, [(37, 53), (7, 9), (1, 1), (1, 3)], N=2, seed=T)
+    exp_r, tol_r = _rpn_sentinel_prediction(case)
+    got = {}
+    for prec in ("bf16", "bf16x3"):
+        m = pkg.RPNHeadSNN(256, 3, T).to(gpu_device)
+        m.precision = prec
+        m.load_state_dict({"shared_conv.weight": case["w_shared"].view(256, 256, 3, 3), "conv_cls.weight": case["w_cls"], "conv_bbox.weight": case["w_bbox"]})
+        lg, bb = m([f.to(gpu_device) for f in case["feats"]])
+        assert _lib.load().snn_debug_last_conv_path() == 1
+        got[prec] = S.rpn_outputs(lg, bb)
+    bad = mx = 0
+    for g_, e, t_ in zip(got["bf16"], exp_r, tol_r):
+        b, m_ = S.check(g_, e, t_)
+        bad, mx = bad + b, max(mx, m_)
+    record_parity("sentinels_rpn_bf16", T=T, max_ulps=round(mx, 3), bad=bad)
+    assert bad == 0, "%d sentinel outputs off the rounded-weight prediction (largest error %.1f ulps)" % (bad, mx)
+    assert S.check_levels(got["bf16x3"], case)[0] == 0                 # the three-plane path meets the UNROUNDED prediction ...
+    off = sum(int((np.abs(g_ - e) > t_)[:, :, S._tap_inside(H, W, 4)].sum()) for g_, e, t_, (H, W) in zip(got["bf16"], case["exp"], case["tol"], case["shapes"]))
+    assert off > 0 and S.check_levels(got["bf16"], case)[0] > 0       # ... which the rounded mode is off, at the sentinel neurons
+    n_live = sum(int((e != 0).sum()) for e in exp_r)
+    differ = sum(int(((a != b) & (e != 0)).sum()) for a, b, e in zip(got["bf16"], got["bf16x3"], exp_r))
+    assert differ >= 0.9 * n_live, (differ, n_live)                    # the outputs of the two modes differ at (nearly) every live sentinel
+
+
+@pytest.mark.parametrize("T,R", [(8, 17), (12, 300), (24, 1)])
+def test_det_sentinels_at_bf16(gpu_device, T, R):
+    import snn_automotive_object_detection_amd as pkg
+    from snn_automotive_object_detection_amd import _lib
+    from tests import _sentinels as S
+    from tests._util import record_parity
+    case = S.det_case(64, 256, 9, T, R, seed=T)
+    order = case["li_order"]
+    kap = S.kappa64(T, order)
+    r = lambda v: float(S._bf16_rn(np.array([v], dtype=np.float32))[0])
+    exp, tol = np.zeros(45), np.zeros(45)
+    for o, hd in enumerate(case["heads"]):                             # chain: constant feature -> fc6 sentinel -> fc7 sentinel -> head, all rounded
+        u7 = hd["src"]
+        u6 = u7["src"]
+        tr6 = S.lif_train(r(u6["weight"]), S.encoder_train(case["feature_values"][u6["d"]], T))
+        tr7 = S.lif_train(r(u7["weight"]), tr6)
+        u = r(hd["u"])
+        exp[o] = S.li_last64(u, tr7, order)[0]
+        tol[o] = S.head_tolerance(int(tr7.sum()), float(np.sum(kap[tr7])) * abs(u))
+    got = {}
+    for prec in ("bf16", "bf16x3"):
+        m = pkg.FastRCNNPredictorSNNFull(64 * 49, 256, 9, T).to(gpu_device)
+        m.precision = prec
+        m.load_state_dict({"fc6.weight": case["w6"], "fc7.weight": case["w7"], "cls_score.weight": case["w_cls"], "bbox_pred.weight": case["w_bbox"]})
+        cls, bbox = m(case["x"].to(gpu_device))
+        assert _lib.load().snn_debug_last_fc6_path() == 1
+        got[prec] = S.det_outputs(cls, bbox)
+    bad, mx = S.check(got["bf16"], np.broadcast_to(exp, (R, 45)), np.broadcast_to(tol, (R, 45)))
+    record_parity("sentinels_det_bf16", T=T, R=R, max_ulps=round(mx, 3), bad=bad)
+    assert bad == 0, "%d sentinel outputs off the rounded-weight prediction (largest error %.1f ulps)" % (bad, mx)
+    assert S.check(got["bf16x3"], case["exp"], case["tol"])[0] == 0
+    assert S.check(got["bf16"], case["exp"], case["tol"])[0] > 0
+    live = np.broadcast_to(exp != 0, (R, 45))
+    assert int(((got["bf16"] != got["bf16x3"]) & live).sum()) >= 0.9 * int(live.sum())
+
+
+# ---- 4. full size against the oracle on rounded weights ------------------------------------------------------------------------------
+LEVELS = [(192, 384), (96, 192), (48, 96), (24, 48), (12, 24)]
+
+
+def test_rpn_head_full_size_vs_oracle_on_rounded_weights(gpu_device):
+    """the Cityscapes pyramid at b = 2, T = 8 (tests/test_gpu_fullsize.py's case): oracle on w.bfloat16().float(), module at "bf16"; 1e-4
+    where the trains agree, flip budget at factor 1.0 (the parity class of bf16x3), tie attribution at TIE_MARGIN on the planes the head
+    itself left in its workspace, integer spike counts"""
+    import snn_automotive_object_detection_amd as S
+    from oracle import snn_oracle as OR
+    from snn_automotive_object_detection_amd import _lib
+    from tests._util import TIE_MARGIN, first_flip_margins, nchw_to_rows, record_parity
+    g = torch.Generator().manual_seed(7)
+    feats = [torch.randn((2, 256, h, w), generator=g) for h, w in LEVELS]
+    torch.manual_seed(1234)
+    m = S.RPNHeadSNN(256, 3, 8)
+    ws, wc, wb = _rnd(m.shared_conv.weight), _rnd(m.conv_cls.weight), _rnd(m.conv_bbox.weight)
+    assert not torch.equal(ws, m.shared_conv.weight.detach())
+    gold_counts = []
+    with torch.no_grad():
+        o_l, o_b = OR.rpn_head_forward(feats, ws, wc, wb, 8, counts_out=gold_counts)
+        _, _, tr = OR.rpn_head_forward([feats[1]], ws, wc, wb, 8, trace=True)
+        _, _, vdec = OR.lif_scan_from_currents(tr[0]["cur"])
+    gold_spk, gold_vdec = nchw_to_rows(tr[0]["spk"]), nchw_to_rows(vdec)
+    del tr, vdec
+    m = m.to(gpu_device)
+    m.precision = "bf16"
+    dev_feats = [f.to(gpu_device) for f in feats]
+    b1, n1 = 2 * LEVELS[0][0] * LEVELS[0][1], 2 * LEVELS[1][0] * LEVELS[1][1]
+    for rates_on in (True, False):                                   # the counting launches, then the default ones
+        m.spike_rates = rates_on
+        out = m(dev_feats)
+        logits, bbox = out[0], out[1]
+        assert _lib.load().snn_debug_last_conv_path() == 1
+        planes = _head_rpn_planes(gpu_device, 8, 256)
+        total = bad = 0
+        for l in range(5):
+            d = torch.maximum((logits[l].cpu() - o_l[l]).abs().amax(dim=1), (bbox[l].cpu() - o_b[l]).abs().amax(dim=1))
+            total += d.numel()
+            bad += int((d > TOL).sum())
+            assert float(d.max()) < 0.05
+            if l == 1:
+                d1 = d.reshape(-1).numpy()
+        budget = flip_budget(total, 256, 8, "rpn_randn", "bf16x3")     # factor 1.0
+        got = planes_to_dense(planes[:, b1: b1 + n1].contiguous(), 256)
+        n_flip, margins, flipped = first_flip_margins(got, gold_spk, gold_vdec)
+        record_parity("bf16_rpn_head_full_size", spike_rates=rates_on, positions_off_tolerance=bad, positions=total, budget=budget, level1_flipped_neurons=n_flip,
+                      worst_margin=float(margins.max()) if n_flip else 0.0)
+        assert bad <= budget, "positions off-tolerance: %d of %d" % (bad, total)
+        assert float(got.mean()) > 0.001
+        assert (margins <= TIE_MARGIN).all(), margins.max()
+        assert flipped.any(axis=1)[np.nonzero(d1 > TOL)[0]].all(), "a position is off tolerance without any flipped hidden spike"
+        if rates_on:
+            counts = m.last_spike_counts.cpu().numpy()
+            worst = 0
+            for l, (h, w) in enumerate(LEVELS):
+                gold = gold_counts[l].numpy()
+                diff = np.abs(counts[l, :2] - gold)
+                worst = max(worst, int(diff.max()))
+                assert counts.dtype.kind == "i" and (diff <= 4 * flip_budget(2 * h * w, 256, 8, "rpn_randn", "bf16x3")).all(), (l, counts[l, :2], gold)
+                assert np.array_equal(out[2][3 * l][:, 0].cpu().numpy(), (counts[l, :2].astype(np.float64) / (8 * 256 * h * w)).astype(np.float32))
+            record_parity("bf16_rpn_head_full_size_counts", worst_count_difference=worst)
+
+
+def test_det_head_full_size_vs_oracle_on_rounded_weights(gpu_device):
+    """2000 RoIs at T = 12: oracle on the rounded weights, module at "bf16"; attribution on the head's own lif6 / lif7 planes"""
+    import snn_automotive_object_detection_amd as S
+    from oracle import snn_oracle as OR
+    from snn_automotive_object_detection_amd import _lib
+    from tests._util import TIE_MARGIN, first_flip_margins, record_parity
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn((2000, 256, 7, 7), generator=g)
+    torch.manual_seed(1235)
+    m = S.FastRCNNPredictorSNNFull(12544, 1024, 9, 12)
+    w = [_rnd(t) for t in (m.fc6.weight, m.fc7.weight, m.cls_score.weight, m.bbox_pred.weight)]
+    with torch.no_grad():
+        o_c, o_b, tr = OR.det_head_forward(x, *w, 12, trace=True)
+    tr = {k: tr[k] for k in ("cur6", "spk6", "cur7", "spk7")}
+    m = m.to(gpu_device)
+    m.precision = "bf16"
+    cls, bbox = m(x.to(gpu_device))
+    assert _lib.load().snn_debug_last_fc6_path() == 1
+    d = torch.maximum((cls.cpu() - o_c).abs().amax(dim=1), (bbox.cpu() - o_b).abs().amax(dim=1))
+    bad = int((d > TOL).sum())
+    budget = flip_budget(2000, 2 * 1024, 12, "det", "bf16x3")
+    p6, p7 = _head_det_planes(gpu_device, 12, 1024, 2000)
+    g6, g7 = planes_to_dense(p6, 1024), planes_to_dense(p7, 1024)
+    _, _, vdec6 = OR.lif_scan_from_currents(tr["cur6"])
+    _, _, vdec7 = OR.lif_scan_from_currents(tr["cur7"])
+    n6, marg6, fl6 = first_flip_margins(g6[:11], tr["spk6"].numpy()[:11], vdec6.numpy()[:11])      # (lif6's last step is a dead time step)
+    roi6 = fl6.any(axis=1)
+    e7 = tr["spk7"].numpy()
+    n7, marg7, fl7 = first_flip_margins(g7[:, ~roi6], e7[:, ~roi6], vdec7.numpy()[:, ~roi6])
+    roi_any = roi6 | (g7 != e7).any(axis=(0, 2))
+    record_parity("bf16_det_head_full_size", rois_off_tolerance=bad, rois=2000, budget=budget, lif6_flipped_neurons=n6, lif7_flipped_neurons_teacher_forced=n7,
+                  worst_margin=float(max([0.0] + list(marg6) + list(marg7))), rois_with_flip=int(roi_any.sum()))
+    assert bad <= budget, bad
+    assert (marg6 <= TIE_MARGIN).all() and (marg7 <= TIE_MARGIN).all(), (marg6, marg7)
+    assert float(g6.mean()) > 0.001 and float(g7.mean()) > 0.001
+    assert roi_any[(d > TOL).numpy()].all(), "a RoI is off tolerance without any flipped hidden spike"
+    assert float(d.max()) < 0.1 and float(d.median()) < 1e-5
+
+
+def test_stress_config_full_canvas_T16_T24_at_bf16(gpu_device):
+    """BASELINE.json config[4] as it is worded - bf16, full canvas, T_rpn = 16 / T_det = 24, spike-rate outputs on - against the oracle on
+    the rounded weights: logits / deltas within 1e-4 up to the flip budget (factor 1.0), spike counts as integers"""
+    import snn_automotive_object_detection_amd as S
+    from oracle import snn_oracle as OR
+    from tests._util import record_parity
+    g = torch.Generator().manual_seed(21)
+    feats = [torch.randn((2, 256, h, w), generator=g) for h, w in LEVELS]
+    m = S.RPNHeadSNN(256, 3, 16)
+    gc = []
+    with torch.no_grad():
+        o_l, o_b, o_r = OR.rpn_head_forward(feats, _rnd(m.shared_conv.weight), _rnd(m.conv_cls.weight), _rnd(m.conv_bbox.weight), 16, spike_rates=True,
+                                            counts_out=gc)
+    m = m.to(gpu_device)
+    m.spike_rates = True
+    m.precision = "bf16"
+    logits, bbox, rates = m([f.to(gpu_device) for f in feats])
+    total = bad = 0
+    for l in range(5):
+        d = torch.maximum((logits[l].cpu() - o_l[l]).abs().amax(1), (bbox[l].cpu() - o_b[l]).abs().amax(1))
+        total += d.numel(); bad += int((d > TOL).sum())
+    budget = flip_budget(total, 256, 16, "rpn_randn", "bf16x3")
+    record_parity("bf16_stress_rpn_full_T16", positions_off_tolerance=bad, positions=total, budget=budget)
+    assert bad <= budget, (bad, total)
+    counts = m.last_spike_counts.cpu().numpy()
+    assert counts.dtype.kind == "i"
+    for l, (h, w) in enumerate(LEVELS):
+        gold = gc[l].numpy()
+        assert (np.abs(counts[l] - gold) <= 4 * flip_budget(2 * h * w, 256, 16, "rpn_in_situ", "bf16x3")).all(), (l, counts[l], gold)
+        for j in (1, 2):
+            assert torch.allclose(rates[3 * l + j].cpu(), o_r[3 * l + j], rtol=1e-4, atol=2e-5)
+        assert torch.equal(rates[3 * l][:, 1].cpu(), o_r[3 * l][:, 1])
+    x = torch.randn((2000, 256, 7, 7), generator=g)
+    d = S.FastRCNNPredictorSNNFull(12544, 1024, 9, 24)
+    w = [_rnd(t) for t in (d.fc6.weight, d.fc7.weight, d.cls_score.weight, d.bbox_pred.weight)]
+    with torch.no_grad():
+        gd = []
+        o_c, o_d = OR.det_head_forward(x, *w, 24, counts_out=gd)
+    d = d.to(gpu_device)
+    d.precision = "bf16"
+    cls, box = d(x.to(gpu_device))
+    off = torch.maximum((cls.cpu() - o_c).abs().amax(1), (box.cpu() - o_d).abs().amax(1))
+    n_off = int((off > TOL).sum())
+    record_parity("bf16_stress_det_full_T24", rois_off_tolerance=n_off, rois=2000, budget=flip_budget(2000, 2 * 1024, 24, "det", "bf16x3"))
+    assert n_off <= flip_budget(2000, 2 * 1024, 24, "det", "bf16x3"), n_off
+    d.spike_rates = True
+    r = d(x.to(gpu_device))
+    c6, c7 = [c.cpu().numpy() for c in d.last_spike_counts]
+    for j, c in enumerate((c6, c7)):
+        gold = gd[j].numpy()
+        assert c.dtype.kind in "iu" and int((c != gold).sum()) <= flip_budget(2000, 1024 * (j + 1), 24, "rpn_in_situ", "bf16x3"), (j, int((c != gold).sum()))
+    assert len(r) == 4 and all(tuple(t.shape) == (2000, 2) for t in r)
+
+
+# ---- 5. the module fixtures: oracle on rounded weights, module at "bf16" ------------------------------------------------------------
+def test_golden_rpn_fixtures_with_rounded_weights(gpu_device):
+    """as tests/test_gpu_modules.py::test_rpn_head_vs_golden, the oracle on the rounded weights in the golden outputs' place: 1e-4 at every
+    position whose hidden train (the planes the head left in its workspace) equals the oracle's; flipped positions inside the budget"""
+    import snn_automotive_object_detection_amd as pkg
+    from oracle import fixtures as FX
+    from oracle import snn_oracle as OR
+    from tests._util import nchw_to_rows
+    for name in sorted(FX.RPN_SPECS):
+        spec = FX.RPN_SPECS[name]
+        feats, w_s, w_c, w_b = FX.rpn_inputs(spec)
+        T, C_ = spec["T"], spec["C"]
+        with torch.no_grad():
+            e_l, e_b, tr = OR.rpn_head_forward([f.clone() for f in feats], _rnd(w_s), _rnd(w_c), _rnd(w_b), T, trace=True)
+        m = pkg.RPNHeadSNN(C_, spec["A"], T).to(gpu_device)
+        m.precision = "bf16"
+        m.load_state_dict({"shared_conv.weight": w_s, "conv_cls.weight": w_c, "conv_bbox.weight": w_b})
+        logits, bbox = m([f.to(gpu_device) for f in feats])
+        planes = _head_rpn_planes(gpu_device, T, C_)
+        base = n_bad = total = 0
+        for l, f in enumerate(feats):
+            N, _, H, W = f.shape
+            got = planes_to_dense(planes[:, base: base + N * H * W].contiguous(), C_)
+            flipped = (got != nchw_to_rows(tr[l]["spk"])).any(axis=(0, 2)).reshape(N, H, W)
+            base += N * H * W
+            n_bad += int(flipped.sum())
+            total += N * H * W
+            ok = ~flipped[:, None, :, :]
+            for o, e in ((logits[l], e_l[l]), (bbox[l], e_b[l])):
+                d = (o.cpu() - e).abs().numpy()
+                assert (d * ok).max() <= TOL, (name, l, float((d * ok).max()))
+                assert d.max() < 0.05
+        assert n_bad <= flip_budget(total, C_, T), (name, n_bad, total)
+
+
+def test_golden_det_fixtures_with_rounded_weights(gpu_device):
+    """as tests/test_gpu_modules.py::test_det_head_vs_golden with the oracle on the rounded weights: 1e-4 at every RoI whose lif6 / lif7
+    trains equal the oracle's"""
+    import snn_automotive_object_detection_amd as pkg
+    from oracle import fixtures as FX
+    from oracle import snn_oracle as OR
+    for name in sorted(FX.DET_SPECS):
+        spec = FX.DET_SPECS[name]
+        x, w6, w7, wc, wb = FX.det_inputs(spec)
+        T, Hd, R = spec["T"], spec["Hd"], x.shape[0]
+        with torch.no_grad():
+            e_cls, e_bbox, tr = OR.det_head_forward(x.clone(), _rnd(w6), _rnd(w7), _rnd(wc), _rnd(wb), T, trace=True)
+        m = pkg.FastRCNNPredictorSNNFull(spec["C"] * 49, Hd, spec["K"], T, only_one_bbox=spec.get("only_one_bbox", False)).to(gpu_device)
+        m.precision = "bf16"
+        m.load_state_dict({"fc6.weight": w6, "fc7.weight": w7, "cls_score.weight": wc, "bbox_pred.weight": wb})
+        cls, bbox = m(x.to(gpu_device))
+        p6, p7 = _head_det_planes(gpu_device, T, Hd, R)
+        n6 = T - 1                                                         # (lif6's spikes of the last step are never read and not formed)
+        bad = (planes_to_dense(p6, Hd)[:n6] != tr["spk6"].numpy()[:n6]).any(axis=(0, 2)) | (planes_to_dense(p7, Hd) != tr["spk7"].numpy()).any(axis=(0, 2))
+        assert bad.sum() <= flip_budget(R, 2 * Hd, T) - 1, (name, int(bad.sum()), R)
+        ok = ~bad[:, None]
+        for o, e in ((cls, e_cls), (bbox, e_bbox)):
+            d = (o.cpu() - e).abs().numpy()
+            assert (d * ok).max() <= TOL, (name, float((d * ok).max()))
+            assert d.max() < 0.1
+
+
+# ---- 7. refusal ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+@pytest.mark.parametrize("which", ["shared_conv", "conv_cls", "fc6", "fc7", "bbox_pred"])
+def test_heads_refuse_non_finite_weights(gpu_device, which, bad):
+    import warnings
+    import snn_automotive_object_detection_amd as pkg
+    from snn_automotive_object_detection_amd import _lib
+    if which in ("shared_conv", "conv_cls"):
+        m = pkg.RPNHeadSNN(64, 3, 8).to(gpu_device)
+        run = lambda: m([torch.randn(1, 64, 16, 16, device=gpu_device)])
+    else:
+        m = pkg.FastRCNNPredictorSNNFull(64 * 49, 128, 9, 12).to(gpu_device)
+        run = lambda: m(torch.rand(40, 64, 7, 7, device=gpu_device))
+    m.precision = "bf16"
+    run()                                                            # fine with finite weights
+    with torch.no_grad():
+        getattr(m, which).weight.view(-1)[11] = bad
+    m.invalidate_packed_weights()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")                               # no fallback warning either: the module raises
+        with pytest.raises(_lib.SnnHipError, match="not finite or round"):
+            run()
+
+
+# ---- 6. through create_model ---------------------------------------------------------------------------------------------------------
+def test_create_model_with_both_heads_at_bf16(gpu_device):
+    """the whole detector with both heads at "bf16" equals the same model at "bf16x3" with pre-rounded head weights, given the same backbone
+    features: the stock convolutions' library kernels do not give the same bits from run to run, so both models read ONE backbone pass"""
+    import copy
+    import snn_automotive_object_detection_amd as pkg
+    torch.manual_seed(11)
+    m1 = pkg.create_model("cityscapes", 9).to(gpu_device).eval()
+    m3 = copy.deepcopy(m1)
+
+    class OnePass(torch.nn.Module):
+        def __init__(self, inner):
+            super().__init__()
+            self.inner, self.out = inner, None
+
+        def forward(self, x):
+            if self.out is None:
+                self.out = self.inner(x)
+            return self.out
+
+    m1.backbone = m3.backbone = OnePass(m1.backbone)
+    heads1 = (m1.rpn.head, m1.roi_heads.box_head_and_predictor)
+    heads3 = (m3.rpn.head, m3.roi_heads.box_head_and_predictor)
+    for h1, h3 in zip(heads1, heads3):
+        h1.precision, h3.precision = "bf16", "bf16x3"
+        with torch.no_grad():
+            for p in h3.parameters():
+                p.copy_(_rnd(p))
+        h3.invalidate_packed_weights()
+        assert all(p.dtype == torch.float32 for p in h1.parameters())
+    g = torch.Generator().manual_seed(12)
+    imgs = [torch.rand(3, 512, 1024, generator=g).to(gpu_device) for _ in range(2)]
+    with torch.no_grad():
+        d1, d3 = m1(imgs), m3(imgs)
+    assert len(d1) == len(d3) == 2
+    for a, b in zip(d1, d3):
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
+    assert all(h._resolve_precision() == "bf16" for h in heads1)
