@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._planes import det_planes as _det_planes, head_det_planes as _head_det_planes, head_rpn_planes as _head_rpn_planes, rpn_planes as _rpn_planes
 from tests._util import planes_to_dense, flip_budget
 
 pytestmark = pytest.mark.gpu
@@ -102,23 +103,6 @@ def _rpn_pair(pkg, dev, C_, A, T, seed):
         heads.append(m)
     assert not torch.equal(ws, _rnd(ws))                            # the mode has something to round
     return heads
-
-
-def _rpn_planes(dev, T, Cw):
-    from snn_automotive_object_detection_amd import _lib, ops
-    off3 = (C.c_uint64 * 3)()
-    _lib.load().snn_debug_last_rpn_planes(off3)
-    P = int(off3[2])
-    return ops._WS.get(dev, 1)[int(off3[0]): int(off3[0]) + T * P * Cw * 4].clone(), int(off3[1])
-
-
-def _det_planes(dev, T, Hd, R):
-    from snn_automotive_object_detection_amd import _lib, ops
-    off3 = (C.c_uint64 * 3)()
-    _lib.load().snn_debug_last_det_planes(off3)
-    n = T * (Hd // 32) * R * 4
-    ws = ops._WS.get(dev, 1)
-    return ws[int(off3[0]): int(off3[0]) + n].clone(), ws[int(off3[1]): int(off3[1]) + n].clone(), int(off3[2])
 
 
 RPN_SHAPES = [(37, 53), (19, 27), (7, 9)]
@@ -230,24 +214,6 @@ def test_readouts_equal_the_three_plane_path_on_rounded_weights(gpu_device):
     for T in (6, 12, 16):
         for a, b in zip(q1[T], q3[T]):
             assert torch.equal(a, b), T
-
-
-def _head_rpn_planes(dev, T, C_):
-    """the shared LIF's spike planes the last RPN forward left in the workspace, as rows [T, P, C / 32] (all levels, position-major)"""
-    from snn_automotive_object_detection_amd import _lib, ops
-    off3 = (C.c_uint64 * 3)()
-    _lib.load().snn_debug_last_rpn_planes(off3)
-    P, Cw = int(off3[2]), (C_ + 31) // 32
-    raw = ops._WS.get(dev, 1)[int(off3[0]): int(off3[0]) + T * P * Cw * 4].view(torch.int32)
-    return (raw.view(T, Cw // 4, P, 4).permute(0, 2, 1, 3).reshape(T, P, Cw) if off3[1] else raw.view(T, P, Cw)).contiguous().clone()
-
-
-def _head_det_planes(dev, T, Hd, R):
-    """lif6 / lif7 spike planes of the last detector forward as rows [T, R, Hd / 32]"""
-    p6, p7, wm = _det_planes(dev, T, Hd, R)
-    p6 = p6.view(torch.int32)
-    p6 = p6.view(T, Hd // 32, R).permute(0, 2, 1).contiguous() if wm else p6.view(T, R, Hd // 32)
-    return p6, p7.view(torch.int32).view(T, R, Hd // 32)
 
 
 # ---- 2. the mode really rounds: sentinel neurons -------------------------------------------------------------------------------------
