@@ -161,6 +161,124 @@ struct LiHeadsArgs {
     Kappa kap;
 };
 
+// shared by the four matrix-core kernels (k_li_heads_mfma / _ksplit and their several-readout forms below):
+// the three bf16 planes of one fp32 weight, w = hi + mid + lo
+__device__ __forceinline__ void lih_split3(const float w, uint16_t& hi, uint16_t& mid, uint16_t& lo) {
+    hi = f2bf_rn(w);
+    const float r1 = __fsub_rn(w, bf2f(hi));
+    mid = f2bf_rn(r1);
+    lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
+}
+// the byte -> 8 bf16 (0 / 1.0) table, 4 KB, by the work-group's 256 threads (the caller's barrier publishes it)
+__device__ __forceinline__ void lih_fill_lut(unsigned char* lut, const int tid) {
+    uint4 q;
+    q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
+    *reinterpret_cast<uint4*>(lut + tid * 16) = q;
+}
+// k_li_heads_mfma / _ro: split W[32kc .. 32kc+31][NOp] into its 3 bf16 planes, into chunk slot `slot` of bbase ([slot][3][NOp][64 B])
+__device__ __forceinline__ void lih_stage(const LiHeadsArgs& a, unsigned char* const bbase, const int tid, const int kc, const int slot) {
+    const int NOp = a.NOp;
+    unsigned char* dst = bbase + (size_t)slot * (3u * NOp * 64u);
+    for (int item = tid; item < 16 * NOp; item += 256) {
+        const int n = item % NOp, kp = item / NOp;
+        const float* src = a.wT + (size_t)(32 * kc + 2 * kp) * a.ldw + a.col0 + n;
+        uint32_t pl[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint16_t hi, mid, lo;
+            lih_split3(src[(size_t)h * a.ldw], hi, mid, lo);
+            pl[0] |= (uint32_t)hi << (16 * h); pl[1] |= (uint32_t)mid << (16 * h); pl[2] |= (uint32_t)lo << (16 * h);
+        }
+        const int off = n * 64 + ((((kp >> 2) ^ G3_SWZ(n)) << 4) | ((kp & 3) << 2));
+#pragma unroll
+        for (int q = 0; q < 3; ++q) *reinterpret_cast<uint32_t*>(dst + q * NOp * 64 + off) = pl[q];
+    }
+}
+// k_li_heads_mfma / _ro: the products acc[t] = spk_(tg0 + t) . W of one group of up to LIH_TG time steps, for the row whose spike words
+// start at wsrc; b_rd = the lane's read position in chunk slot 0.  TN (the steps whose accumulators exist) is a COMPILE-TIME constant: 8,
+// or 4 / 2 / 1 for a shorter last group; steps past the group's real count tn < TN multiply all-zero spike words (exact: their sums stay 0).
+// (Until round 4 the loops tested t < tn at run time; the compiler specialised the unrolled chunks on tn itself, and its tn == 2
+// variant of the Kc == 8 path returned wrong sums in accumulator register 3 - rows 3 mod 4 of every tile, T = 2, 10, 18, 26 at
+// C = 256; nothing here depends on run-time control flow around the MFMAs any more.  tests/test_gpu_stages.py sweeps T = 1 .. 26.)
+// With W streamed the whole work-group must call this together (it stages and has the barriers of the double buffer).
+template <int TN, int NT>
+__device__ __forceinline__ void lih_mfma_products(const LiHeadsArgs& a, const unsigned char* const lut, unsigned char* const bbase,
+                                                  const unsigned char* const b_rd, const uint32_t* const wsrc, const int tid, const int lg8,
+                                                  const int tg0, const int tn, f32x4 (&acc)[TN][NT]) {
+    const int NOp = a.NOp, Kc = a.Kw;
+    const uint32_t slot_bytes = 3u * NOp * 64u;
+#pragma unroll
+    for (int t = 0; t < TN; ++t)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto chunk = [&](int kc, const uint32_t (&w_cur)[TN]) {
+        const unsigned char* bs = b_rd + (size_t)(a.resident ? kc : (kc & 1)) * slot_bytes;
+        bf16x8 b[3][NT];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                b[pl][nt] = *reinterpret_cast<const bf16x8*>(bs + (pl * NOp + nt * 16) * 64);
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+            const bf16x8 af = *reinterpret_cast<const bf16x8*>(lut + (__builtin_amdgcn_ubfe(w_cur[t], lg8, 8) << 4));
+#pragma unroll
+            for (int pl = 2; pl >= 0; --pl)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[pl][nt], acc[t][nt], 0, 0, 0);
+        }
+    };
+    if (a.resident && Kc == 8) {
+        // C = 256: the 8 spike words of a (t, row) are one 32-byte line - all T x 8 words are requested up
+        // front (one memory latency per row tile instead of one per chunk)
+        uint4 wl[TN][2];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+            const uint4* q = reinterpret_cast<const uint4*>(wsrc + (size_t)(tg0 + (t < tn ? t : 0)) * a.spk_stride);
+            wl[t][0] = q[0]; wl[t][1] = a.half_split ? q[(size_t)a.M] : q[1];     // second half: M x 16 bytes on
+            if (t >= tn) { wl[t][0] = uint4{0u, 0u, 0u, 0u}; wl[t][1] = uint4{0u, 0u, 0u, 0u}; }
+        }
+#pragma unroll
+        for (int kc = 0; kc < 8; ++kc) {
+            uint32_t w_cur[TN];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) {
+                const uint4 v = wl[t][kc >> 2];
+                w_cur[t] = (kc & 3) == 0 ? v.x : (kc & 3) == 1 ? v.y : (kc & 3) == 2 ? v.z : v.w;
+            }
+            chunk(kc, w_cur);
+        }
+    } else {
+        uint32_t w_nxt[TN];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride] : 0u;
+        if (!a.resident) { lih_stage(a, bbase, tid, 0, 0); __syncthreads(); }
+        for (int kc = 0; kc < Kc; ++kc) {
+            uint32_t w_cur[TN];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) w_cur[t] = w_nxt[t];
+            if (kc + 1 < Kc) {
+#pragma unroll
+                for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride + kc + 1] : 0u;
+                if (!a.resident) lih_stage(a, bbase, tid, kc + 1, (kc + 1) & 1);
+            }
+            chunk(kc, w_cur);
+            if (!a.resident) __syncthreads();           // chunk kc+1 staged, chunk kc consumed
+        }
+    }
+}
+// the tn -> TN ladder of a time group (tn block-uniform): group(std::integral_constant<int, TN>, tg0, tn) with TN = TM (where a group
+// holds TM > 8 steps), 8, 4, 2 or 1 >= tn.  Textual, so that each kernel's always_inline group body is expanded as if written in place.
+#define LIH_TN_LADDER(TM, group, tg0, tn)                                                        \
+    do {                                                                                         \
+        if ((TM) > 8 && (tn) > 8) group(std::integral_constant<int, (TM)>{}, tg0, tn);           \
+        else if ((tn) > 4) group(std::integral_constant<int, 8>{}, tg0, tn);                     \
+        else if ((tn) > 2) group(std::integral_constant<int, 4>{}, tg0, tn);                     \
+        else if ((tn) == 2) group(std::integral_constant<int, 2>{}, tg0, tn);                    \
+        else group(std::integral_constant<int, 1>{}, tg0, tn);                                   \
+    } while (0)
+
 template <int NT>
 __global__ __launch_bounds__(256) void k_li_heads_mfma(const LiHeadsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -168,35 +286,9 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma(const LiHeadsArgs a) {
     unsigned char* const bbase = smem + G3_LUT_BYTES;          // [chunk slot][3][NOp][64 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
-    const int NOp = a.NOp, Kc = a.Kw;
-    const uint32_t slot_bytes = 3u * NOp * 64u;
-    {
-        uint4 q;
-        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
-        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
-    }
-    auto stage = [&](int kc, int slot) {                       // split W[32kc .. 32kc+31][NOp] into 3 bf16 planes
-        unsigned char* dst = bbase + (size_t)slot * slot_bytes;
-        for (int item = tid; item < 16 * NOp; item += 256) {
-            const int n = item % NOp, kp = item / NOp;
-            const float* src = a.wT + (size_t)(32 * kc + 2 * kp) * a.ldw + a.col0 + n;
-            uint32_t pl[3] = {0u, 0u, 0u};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float w = src[(size_t)h * a.ldw];
-                const uint16_t hi = f2bf_rn(w);
-                const float r1 = __fsub_rn(w, bf2f(hi));
-                const uint16_t mid = f2bf_rn(r1);
-                const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
-                pl[0] |= (uint32_t)hi << (16 * h); pl[1] |= (uint32_t)mid << (16 * h); pl[2] |= (uint32_t)lo << (16 * h);
-            }
-            const int off = n * 64 + ((((kp >> 2) ^ G3_SWZ(n)) << 4) | ((kp & 3) << 2));
-#pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint32_t*>(dst + q * NOp * 64 + off) = pl[q];
-        }
-    };
+    lih_fill_lut(lut, tid);
     if (a.resident)
-        for (int kc = 0; kc < Kc; ++kc) stage(kc, kc);
+        for (int kc = 0; kc < a.Kw; ++kc) lih_stage(a, bbase, tid, kc, kc);
     __syncthreads();
     const unsigned char* const b_rd = bbase + lr * 64 + ((lg ^ G3_SWZ(lr)) << 4);
     for (int g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
@@ -206,74 +298,10 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma(const LiHeadsArgs a) {
         f32x4 o_last[NT], o_sum[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) { o_last[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; o_sum[nt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        // One group of up to LIH_TG time steps.  TN (the steps whose accumulators exist) is a COMPILE-TIME constant: 8, or 4 / 2 / 1 for a
-        // shorter last group; steps past the group's real count tn < TN multiply all-zero spike words (exact: their sums stay 0).
-        // (Until round 4 the loops tested t < tn at run time; the compiler specialised the unrolled chunks on tn itself, and its tn == 2
-        // variant of the Kc == 8 path returned wrong sums in accumulator register 3 - rows 3 mod 4 of every tile, T = 2, 10, 18, 26 at
-        // C = 256; nothing here depends on run-time control flow around the MFMAs any more.  tests/test_gpu_stages.py sweeps T = 1 .. 26.)
         auto group = [&](auto tn_c, const int tg0, const int tn) __attribute__((always_inline)) {
             constexpr int TN = decltype(tn_c)::value;
             f32x4 acc[TN][NT];
-#pragma unroll
-            for (int t = 0; t < TN; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            auto chunk = [&](int kc, const uint32_t (&w_cur)[TN]) {
-                const unsigned char* bs = b_rd + (size_t)(a.resident ? kc : (kc & 1)) * slot_bytes;
-                bf16x8 b[3][NT];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        b[pl][nt] = *reinterpret_cast<const bf16x8*>(bs + (pl * NOp + nt * 16) * 64);
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const bf16x8 af = *reinterpret_cast<const bf16x8*>(lut + (__builtin_amdgcn_ubfe(w_cur[t], lg8, 8) << 4));
-#pragma unroll
-                    for (int pl = 2; pl >= 0; --pl)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[pl][nt], acc[t][nt], 0, 0, 0);
-                }
-            };
-            if (a.resident && Kc == 8) {
-                // C = 256: the 8 spike words of a (t, row) are one 32-byte line - all T x 8 words are requested up
-                // front (one memory latency per row tile instead of one per chunk)
-                uint4 wl[TN][2];
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const uint4* q = reinterpret_cast<const uint4*>(wsrc + (size_t)(tg0 + (t < tn ? t : 0)) * a.spk_stride);
-                    wl[t][0] = q[0]; wl[t][1] = a.half_split ? q[(size_t)a.M] : q[1];     // second half: M x 16 bytes on
-                    if (t >= tn) { wl[t][0] = uint4{0u, 0u, 0u, 0u}; wl[t][1] = uint4{0u, 0u, 0u, 0u}; }
-                }
-#pragma unroll
-                for (int kc = 0; kc < 8; ++kc) {
-                    uint32_t w_cur[TN];
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) {
-                        const uint4 v = wl[t][kc >> 2];
-                        w_cur[t] = (kc & 3) == 0 ? v.x : (kc & 3) == 1 ? v.y : (kc & 3) == 2 ? v.z : v.w;
-                    }
-                    chunk(kc, w_cur);
-                }
-            } else {
-                uint32_t w_nxt[TN];
-#pragma unroll
-                for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride] : 0u;
-                if (!a.resident) { stage(0, 0); __syncthreads(); }
-                for (int kc = 0; kc < Kc; ++kc) {
-                    uint32_t w_cur[TN];
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) w_cur[t] = w_nxt[t];
-                    if (kc + 1 < Kc) {
-#pragma unroll
-                        for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride + kc + 1] : 0u;
-                        if (!a.resident) stage(kc + 1, (kc + 1) & 1);
-                    }
-                    chunk(kc, w_cur);
-                    if (!a.resident) __syncthreads();           // chunk kc+1 staged, chunk kc consumed
-                }
-            }
+            lih_mfma_products<TN, NT>(a, lut, bbase, b_rd, wsrc, tid, lg8, tg0, tn, acc);
 #pragma unroll
             for (int t = 0; t < TN; ++t) {
                 const int ti = min(tg0 + t, a.T - 1);           // (steps past tn: their accumulators are zero)
@@ -289,10 +317,7 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma(const LiHeadsArgs a) {
         };
         for (int tg0 = 0; tg0 < a.T; tg0 += LIH_TG) {
             const int tn = min(LIH_TG, a.T - tg0);              // block-uniform
-            if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
-            else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
-            else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
-            else group(std::integral_constant<int, 1>{}, tg0, tn);
+            LIH_TN_LADDER(LIH_TG, group, tg0, tn);
         }
         // lane holds rows lg*4 + r, output column nt*16 + lr
 #pragma unroll
@@ -320,6 +345,28 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma(const LiHeadsArgs a) {
 // values requested before this chunk's MFMAs), and needs no barrier until the four partial results meet in LDS and are
 // added in wave order (deterministic).  2000 x 1024 x 45, T = 12: 68 us (fp32 VALU kernel) -> ~15 us.
 #define LIH_KS_TM(nt) ((nt) <= 2 ? 16 : 12)     // time steps per group: accumulators beside NT column tiles
+// k_li_heads_ksplit / _ro: the four waves' partial chains meet in LDS (red: [4 waves][2][NT][64 lanes]) and are added in wave order
+// (deterministic).  lih_ks_publish is called by the whole work-group (one barrier), then wave 0 sums each column tile; the caller's
+// next barrier frees red.
+template <int NT>
+__device__ __forceinline__ void lih_ks_publish(f32x4* const red, const int wave, const int lane, const f32x4 (&o_last)[NT], const f32x4 (&o_sum)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        red[((wave * 2 + 0) * NT + nt) * 64 + lane] = o_last[nt];
+        red[((wave * 2 + 1) * NT + nt) * 64 + lane] = o_sum[nt];
+    }
+    __syncthreads();
+}
+template <int NT>
+__device__ __forceinline__ void lih_ks_sum(const f32x4* const red, const int lane, const int nt, f32x4& ol, f32x4& os) {
+    ol = red[(0 * NT + nt) * 64 + lane]; os = red[(1 * NT + nt) * 64 + lane];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const f32x4 pl = red[((w * 2 + 0) * NT + nt) * 64 + lane], ps = red[((w * 2 + 1) * NT + nt) * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { ol[r] = __fadd_rn(ol[r], pl[r]); os[r] = __fadd_rn(os[r], ps[r]); }
+    }
+}
 template <int NT>
 __global__ __launch_bounds__(256) void k_li_heads_ksplit(const LiHeadsArgs a) {
     constexpr int TM = LIH_KS_TM(NT);
@@ -330,11 +377,7 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit(const LiHeadsArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
     const int NOp = a.NOp, Kc = a.Kw, T = a.T;
-    {
-        uint4 q;
-        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
-        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
-    }
+    lih_fill_lut(lut, tid);
     __syncthreads();
     const int m0 = blockIdx.x * 16;
     const int mrow = min(m0 + lr, a.M - 1);                    // rows past M: recomputed, never stored
@@ -372,11 +415,8 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit(const LiHeadsArgs a) {
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float w = wf[nt][j];
-                    const uint16_t hi = f2bf_rn(w);
-                    const float r1 = __fsub_rn(w, bf2f(hi));
-                    const uint16_t mid = f2bf_rn(r1);
-                    const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
+                    uint16_t hi, mid, lo;
+                    lih_split3(wf[nt][j], hi, mid, lo);
                     b[0][nt][j] = (short)hi; b[1][nt][j] = (short)mid; b[2][nt][j] = (short)lo;
                 }
             uint32_t w_cur[TN];
@@ -408,28 +448,14 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit(const LiHeadsArgs a) {
     };
     for (int tg0 = 0; tg0 < T; tg0 += TM) {
         const int tn = min(TM, T - tg0);                        // block-uniform
-        if (tn > 8) group(std::integral_constant<int, TM>{}, tg0, tn);
-        else if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
-        else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
-        else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
-        else group(std::integral_constant<int, 1>{}, tg0, tn);
+        LIH_TN_LADDER(TM, group, tg0, tn);
     }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        red[((wave * 2 + 0) * NT + nt) * 64 + lane] = o_last[nt];
-        red[((wave * 2 + 1) * NT + nt) * 64 + lane] = o_sum[nt];
-    }
-    __syncthreads();
+    lih_ks_publish<NT>(red, wave, lane, o_last, o_sum);
     if (wave != 0) return;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        f32x4 ol = red[(0 * NT + nt) * 64 + lane], os = red[(1 * NT + nt) * 64 + lane];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const f32x4 pl = red[((w * 2 + 0) * NT + nt) * 64 + lane], ps = red[((w * 2 + 1) * NT + nt) * 64 + lane];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { ol[r] = __fadd_rn(ol[r], pl[r]); os[r] = __fadd_rn(os[r], ps[r]); }
-        }
+        f32x4 ol, os;
+        lih_ks_sum<NT>(red, lane, nt, ol, os);
         // lane holds rows lg*4 + r, output column nt*16 + lr
         const int j = a.col0 + nt * 16 + lr;
 #pragma unroll
@@ -521,35 +547,9 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma_ro(const LiReadoutArgs ra
     unsigned char* const bbase = smem + G3_LUT_BYTES;          // [chunk slot][3][NOp][64 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
-    const int NOp = a.NOp, Kc = a.Kw;
-    const uint32_t slot_bytes = 3u * NOp * 64u;
-    {
-        uint4 q;
-        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
-        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
-    }
-    auto stage = [&](int kc, int slot) {                       // as k_li_heads_mfma
-        unsigned char* dst = bbase + (size_t)slot * slot_bytes;
-        for (int item = tid; item < 16 * NOp; item += 256) {
-            const int n = item % NOp, kp = item / NOp;
-            const float* src = a.wT + (size_t)(32 * kc + 2 * kp) * a.ldw + a.col0 + n;
-            uint32_t pl[3] = {0u, 0u, 0u};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float w = src[(size_t)h * a.ldw];
-                const uint16_t hi = f2bf_rn(w);
-                const float r1 = __fsub_rn(w, bf2f(hi));
-                const uint16_t mid = f2bf_rn(r1);
-                const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
-                pl[0] |= (uint32_t)hi << (16 * h); pl[1] |= (uint32_t)mid << (16 * h); pl[2] |= (uint32_t)lo << (16 * h);
-            }
-            const int off = n * 64 + ((((kp >> 2) ^ G3_SWZ(n)) << 4) | ((kp & 3) << 2));
-#pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint32_t*>(dst + q * NOp * 64 + off) = pl[q];
-        }
-    };
+    lih_fill_lut(lut, tid);
     if (a.resident)
-        for (int kc = 0; kc < Kc; ++kc) stage(kc, kc);
+        for (int kc = 0; kc < a.Kw; ++kc) lih_stage(a, bbase, tid, kc, kc);
     __syncthreads();
     const unsigned char* const b_rd = bbase + lr * 64 + ((lg ^ G3_SWZ(lr)) << 4);
     for (int g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
@@ -564,72 +564,12 @@ __global__ __launch_bounds__(256) void k_li_heads_mfma_ro(const LiReadoutArgs ra
         auto group = [&](auto tn_c, const int tg0, const int tn) __attribute__((always_inline)) {
             constexpr int TN = decltype(tn_c)::value;
             f32x4 acc[TN][NT];
-#pragma unroll
-            for (int t = 0; t < TN; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            auto chunk = [&](int kc, const uint32_t (&w_cur)[TN]) {
-                const unsigned char* bs = b_rd + (size_t)(a.resident ? kc : (kc & 1)) * slot_bytes;
-                bf16x8 b[3][NT];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        b[pl][nt] = *reinterpret_cast<const bf16x8*>(bs + (pl * NOp + nt * 16) * 64);
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const bf16x8 af = *reinterpret_cast<const bf16x8*>(lut + (__builtin_amdgcn_ubfe(w_cur[t], lg8, 8) << 4));
-#pragma unroll
-                    for (int pl = 2; pl >= 0; --pl)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, b[pl][nt], acc[t][nt], 0, 0, 0);
-                }
-            };
-            if (a.resident && Kc == 8) {
-                uint4 wl[TN][2];
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const uint4* q = reinterpret_cast<const uint4*>(wsrc + (size_t)(tg0 + (t < tn ? t : 0)) * a.spk_stride);
-                    wl[t][0] = q[0]; wl[t][1] = a.half_split ? q[(size_t)a.M] : q[1];
-                    if (t >= tn) { wl[t][0] = uint4{0u, 0u, 0u, 0u}; wl[t][1] = uint4{0u, 0u, 0u, 0u}; }
-                }
-#pragma unroll
-                for (int kc = 0; kc < 8; ++kc) {
-                    uint32_t w_cur[TN];
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) {
-                        const uint4 v = wl[t][kc >> 2];
-                        w_cur[t] = (kc & 3) == 0 ? v.x : (kc & 3) == 1 ? v.y : (kc & 3) == 2 ? v.z : v.w;
-                    }
-                    chunk(kc, w_cur);
-                }
-            } else {
-                uint32_t w_nxt[TN];
-#pragma unroll
-                for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride] : 0u;
-                if (!a.resident) { stage(0, 0); __syncthreads(); }
-                for (int kc = 0; kc < Kc; ++kc) {
-                    uint32_t w_cur[TN];
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) w_cur[t] = w_nxt[t];
-                    if (kc + 1 < Kc) {
-#pragma unroll
-                        for (int t = 0; t < TN; ++t) w_nxt[t] = t < tn ? wsrc[(size_t)(tg0 + t) * a.spk_stride + kc + 1] : 0u;
-                        if (!a.resident) stage(kc + 1, (kc + 1) & 1);
-                    }
-                    chunk(kc, w_cur);
-                    if (!a.resident) __syncthreads();
-                }
-            }
+            lih_mfma_products<TN, NT>(a, lut, bbase, b_rd, wsrc, tid, lg8, tg0, tn, acc);
             lih_ro_fold<TN, NT, RB, S>(ra, tg0, acc, o_last, o_sum);
         };
         for (int tg0 = 0; tg0 < a.T; tg0 += LIH_TG) {
             const int tn = min(LIH_TG, a.T - tg0);              // block-uniform
-            if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
-            else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
-            else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
-            else group(std::integral_constant<int, 1>{}, tg0, tn);
+            LIH_TN_LADDER(LIH_TG, group, tg0, tn);
         }
 #pragma unroll
         for (int j = 0; j < RB; ++j)
@@ -648,11 +588,7 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit_ro(const LiReadoutArgs 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lg = lane >> 4, lg8 = 8 * lg;
     const int Kc = a.Kw, T = a.T;
-    {
-        uint4 q;
-        q.x = bf16_pair(tid, 0); q.y = bf16_pair(tid, 1); q.z = bf16_pair(tid, 2); q.w = bf16_pair(tid, 3);
-        *reinterpret_cast<uint4*>(lut + tid * 16) = q;
-    }
+    lih_fill_lut(lut, tid);
     __syncthreads();
     const int m0 = blockIdx.x * 16;
     const int mrow = min(m0 + lr, a.M - 1);                    // rows past M: recomputed, never stored
@@ -688,11 +624,8 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit_ro(const LiReadoutArgs 
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float w = wf[nt][j];
-                    const uint16_t hi = f2bf_rn(w);
-                    const float r1 = __fsub_rn(w, bf2f(hi));
-                    const uint16_t mid = f2bf_rn(r1);
-                    const uint16_t lo = f2bf_rn(__fsub_rn(r1, bf2f(mid)));
+                    uint16_t hi, mid, lo;
+                    lih_split3(wf[nt][j], hi, mid, lo);
                     b[0][nt][j] = (short)hi; b[1][nt][j] = (short)mid; b[2][nt][j] = (short)lo;
                 }
             uint32_t w_cur[TN];
@@ -713,37 +646,20 @@ __global__ __launch_bounds__(256) void k_li_heads_ksplit_ro(const LiReadoutArgs 
     };
     for (int tg0 = 0; tg0 < T; tg0 += TM) {
         const int tn = min(TM, T - tg0);                        // block-uniform
-        if (tn > 8) group(std::integral_constant<int, TM>{}, tg0, tn);
-        else if (tn > 4) group(std::integral_constant<int, 8>{}, tg0, tn);
-        else if (tn > 2) group(std::integral_constant<int, 4>{}, tg0, tn);
-        else if (tn == 2) group(std::integral_constant<int, 2>{}, tg0, tn);
-        else group(std::integral_constant<int, 1>{}, tg0, tn);
+        LIH_TN_LADDER(TM, group, tg0, tn);
     }
     // per readout: the four waves' partial chains meet in LDS and are added in wave order, as in k_li_heads_ksplit
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
         if (j >= ra.n_ro) break;                               // block-uniform
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            red[((wave * 2 + 0) * NT + nt) * 64 + lane] = o_last[j][nt];
-            red[((wave * 2 + 1) * NT + nt) * 64 + lane] = o_sum[j][nt];
-        }
-        __syncthreads();
+        lih_ks_publish<NT>(red, wave, lane, o_last[j], o_sum[j]);
         if (wave == 0) {
             f32x4 ol[NT], os[NT];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                ol[nt] = red[(0 * NT + nt) * 64 + lane]; os[nt] = red[(1 * NT + nt) * 64 + lane];
-#pragma unroll
-                for (int w = 1; w < 4; ++w) {
-                    const f32x4 pl = red[((w * 2 + 0) * NT + nt) * 64 + lane], ps = red[((w * 2 + 1) * NT + nt) * 64 + lane];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { ol[nt][r] = __fadd_rn(ol[nt][r], pl[r]); os[nt][r] = __fadd_rn(os[nt][r], ps[r]); }
-                }
-            }
+            for (int nt = 0; nt < NT; ++nt) lih_ks_sum<NT>(red, lane, nt, ol[nt], os[nt]);
             lih_ro_store<NT, S>(ra, j, m0, lg, lr, ol, os);
         }
-        __syncthreads();
+        __syncthreads();                                       // red is free for the next readout
     }
 }
 

@@ -1599,62 +1599,97 @@ int snn_lif_scan(const float* cur, int T, int R, int N, int ldc, const snn_param
     return lif_scan_window(cur, T, lif_window_all(T), R, N, ldc, p, spk, spk_stride, row_counts, s);
 }
 
+// all of W as three bf16 planes stays resident in LDS (k_li_heads_mfma)
+static bool li_heads_fits(int Kw, int NOp) { return (size_t)Kw * 3 * NOp * 64 <= 96 * 1024; }
+
 // the launch of snn_li_heads that can read spike planes in blocks of four words (k_li_heads_mfma with W resident, 8 words per row)
 static bool li_heads_reads_split(int K, int NA, int NB) {
     const int Kw = cdiv(K, 32), NOp = cdiv(NA + NB, 16) * 16;
     const int force = knobs().li_heads;
-    return Kw == 8 && NOp <= 64 && (size_t)Kw * 3 * NOp * 64 <= 96 * 1024 && (force == 0 || force == 2);
+    return Kw == 8 && NOp <= 64 && li_heads_fits(Kw, NOp) && (force == 0 || force == 2);
 }
 
 // which kernel takes columns col0 .. col0 + NOp - 1 of the heads: 3 k_li_heads_ksplit, 2 k_li_heads_mfma, 1 k_li_heads (fp32 VALU)
 static int li_heads_kind(int Kw, int NOp, int force) {
     // matrix-core kernel where all of W (as three bf16 planes) stays resident in LDS; the streamed form is latency
     // bound on small row counts (detector heads: 164 us against 88 us for the VALU kernel) and only runs when forced
-    const bool fits = (size_t)Kw * 3 * NOp * 64 <= 96 * 1024;
+    const bool fits = li_heads_fits(Kw, NOp);
     if (NOp <= 64 && Kw >= 4 && (force ? force == 3 : !fits)) return 3;
     if (NOp <= 64 && (force ? force == 2 : fits)) return 2;
     return 1;
 }
 
+// what the launches of one heads call (single- or several-readout) share
+struct LiHeadsCall {
+    const uint32_t* spk; size_t spk_stride;
+    const float* w;
+    int M, Kw, NA, NB;
+    bool half_split;
+    int ldw;                      // columns of a row of the packed matrix
+    int force;                    // debug / A-B knob: 1 "valu" forces the fp32 VALU kernel, 2 "mfma", 3 "ksplit"; SNN_PRECISION_F32_STRICT always takes the VALU kernel
+    int step;                     // columns per launch
+};
+static int li_heads_call(LiHeadsCall* c, const uint32_t* spk, size_t spk_stride, int M, int K, const float* w_heads_packed, int NA, int NB,
+                         const snn_params* p, bool half_split) {
+    // (covers more than 64 outputs per row as well: the split planes go with one launch)
+    if (half_split && !li_heads_reads_split(K, NA, NB)) return fail(-1, "snn_li_heads: split planes need the resident matrix-core kernel");
+    c->spk = spk; c->spk_stride = spk_stride; c->w = w_heads_packed; c->M = M; c->Kw = cdiv(K, 32); c->NA = NA; c->NB = NB;
+    c->half_split = half_split;
+    c->ldw = cdiv(NA + NB, 16) * 16;
+    c->force = (p && p->precision == SNN_PRECISION_F32_STRICT) ? 1 : knobs().li_heads;      // (a null p: the caller's argument check refuses it)
+    // More than 64 outputs per row (num_classes >= 13: 5 K outputs - pascal 24, coco 91 of the reference's configs): one launch per
+    // block of 64 columns (matrix-core kernels; the VALU kernel takes 256); every launch reads all spike planes, which is the small
+    // operand here.  (Until round 4: the VALU kernel up to 256 outputs, an error beyond.)
+    c->step = c->force == 1 ? 256 : 64;
+    return 0;
+}
+
+// a matrix-core launch (kind 3 / 2, single- or several-readout kernel) over columns col0 .. col0 + NOp - 1: its arguments but for T and
+// kap, which are the caller's; returns its LDS bytes
+static size_t li_heads_plan(int kind, const LiHeadsCall& c, float* out_a, float* out_b, float* sum_a, float* sum_b, int col0, int NOp,
+                            LiHeadsArgs* a) {
+    memset(a, 0, sizeof(*a));
+    a->spk = c.spk; a->spk_stride = c.spk_stride; a->wT = c.w; a->out_a = out_a; a->out_b = out_b; a->sum_a = sum_a; a->sum_b = sum_b;
+    a->M = c.M; a->Kw = c.Kw; a->NOp = NOp; a->NA = c.NA; a->NB = c.NB; a->ldw = c.ldw; a->col0 = col0;
+    if (kind == 3) return G3_LUT_BYTES + (size_t)4 * 2 * (NOp / 16) * 64 * 16;
+    a->n_groups = cdiv(c.M, 64);
+    a->half_split = c.half_split;
+    a->resident = li_heads_fits(c.Kw, NOp);
+    return G3_LUT_BYTES + (size_t)(a->resident ? c.Kw : 2) * 3 * NOp * 64;
+}
+
+// work-groups of a k_li_heads_mfma / k_li_heads_mfma_ro launch.  Resident weights: persistent work-groups (staging once per work-group),
+// exactly as many as are co-resident (k_li_heads_mfma: registers allow 3 per SIMD: a grid of 4 per CU ran a third of them as a second,
+// mostly empty round); streamed: one row group each.  per_cu: the co-resident work-groups per CU if the caller keeps them (the plain
+// launch, which is on the timed path), else 0: asked here, `fallback` where the query fails.
+static int li_heads_grid(const LiHeadsArgs& a, const void* kern, size_t lds, int per_cu, int fallback) {
+    if (!a.resident) return a.n_groups;
+    if (per_cu <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess || per_cu <= 0)) per_cu = fallback;
+    return min(a.n_groups, per_cu * g3_slots());
+}
+
 // columns col0 .. col0 + NOp - 1 (NOp a multiple of 16, <= 64 for the matrix-core kernels, <= 256 for the VALU kernel) of the heads
-static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, int Kw, const float* w_heads_packed, int NA, int NB,
-                         const Kappa& kap, float* out_a, float* out_b, float* sum_a, float* sum_b, bool half_split, int force,
-                         int ldw, int col0, int NOp, hipStream_t s) {
-    const int kind = li_heads_kind(Kw, NOp, force);
-    // W too large for LDS: one work-group per 16 rows, the reduction split over its 4 waves ("ksplit" forces it)
-    if (kind == 3) {
+static int li_heads_cols(const LiHeadsCall& c, int T, const Kappa& kap, float* out_a, float* out_b, float* sum_a, float* sum_b, int col0,
+                         int NOp, hipStream_t s) {
+    const int kind = li_heads_kind(c.Kw, NOp, c.force), nt = NOp / 16, M = c.M;
+    if (kind != 1) {
         LiHeadsArgs a;
-        memset(&a, 0, sizeof(a));
-        a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
-        a.sum_a = sum_a; a.sum_b = sum_b; a.T = T; a.M = M; a.Kw = Kw; a.NOp = NOp; a.NA = NA; a.NB = NB; a.kap = kap; a.ldw = ldw; a.col0 = col0;
-        const int nt = NOp / 16;
-        const size_t lds = G3_LUT_BYTES + (size_t)4 * 2 * nt * 64 * 16;
-        const void* kern = nt == 1 ? (const void*)k_li_heads_ksplit<1> : nt == 2 ? (const void*)k_li_heads_ksplit<2>
-                         : nt == 3 ? (const void*)k_li_heads_ksplit<3> : (const void*)k_li_heads_ksplit<4>;
+        const size_t lds = li_heads_plan(kind, c, out_a, out_b, sum_a, sum_b, col0, NOp, &a);
+        a.T = T; a.kap = kap;
         void* kargs[] = {(void*)&a};
-        hipError_t e = hipLaunchKernel(kern, dim3(cdiv(M, 16)), dim3(256), kargs, lds, s);
-        if (e != hipSuccess) return fail(-3, "k_li_heads_ksplit launch failed: %s", hipGetErrorString(e));
-        SNN_CHECK_LAUNCH("k_li_heads_ksplit");
-        return 0;
-    }
-    if (kind == 2) {
-        LiHeadsArgs a;
-        memset(&a, 0, sizeof(a));
-        a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
-        a.sum_a = sum_a; a.sum_b = sum_b; a.T = T; a.M = M; a.Kw = Kw; a.NOp = NOp; a.NA = NA; a.NB = NB; a.kap = kap; a.ldw = ldw; a.col0 = col0;
-        a.n_groups = cdiv(M, 64);
-        a.half_split = half_split;
-        const size_t all = (size_t)Kw * 3 * NOp * 64;
-        a.resident = all <= 96 * 1024;
-        const size_t lds = G3_LUT_BYTES + (a.resident ? all : (size_t)2 * 3 * NOp * 64);
-        const int nt = NOp / 16;
+        // W too large for LDS: one work-group per 16 rows, the reduction split over its 4 waves ("ksplit" forces it)
+        if (kind == 3) {
+            const void* kern = nt == 1 ? (const void*)k_li_heads_ksplit<1> : nt == 2 ? (const void*)k_li_heads_ksplit<2>
+                             : nt == 3 ? (const void*)k_li_heads_ksplit<3> : (const void*)k_li_heads_ksplit<4>;
+            hipError_t e = hipLaunchKernel(kern, dim3(cdiv(M, 16)), dim3(256), kargs, lds, s);
+            if (e != hipSuccess) return fail(-3, "k_li_heads_ksplit launch failed: %s", hipGetErrorString(e));
+            SNN_CHECK_LAUNCH("k_li_heads_ksplit");
+            return 0;
+        }
         const void* kern = nt == 1 ? (const void*)k_li_heads_mfma<1> : nt == 2 ? (const void*)k_li_heads_mfma<2>
                          : nt == 3 ? (const void*)k_li_heads_mfma<3> : (const void*)k_li_heads_mfma<4>;
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        // resident weights: persistent work-groups (staging once per work-group), exactly as many as are co-resident
-        // (registers allow 3 per SIMD: a grid of 4 per CU ran a third of them as a second, mostly empty round);
-        // streamed: one row group each
         static int per_cu_cache[5] = {0, 0, 0, 0, 0};           // by column tiles; the LDS size of the resident form follows from them and Kw
         static size_t per_cu_lds[5] = {0, 0, 0, 0, 0};
         if (per_cu_cache[nt] == 0 || per_cu_lds[nt] != lds) {
@@ -1662,10 +1697,7 @@ static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, i
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v <= 0) v = 3;
             per_cu_cache[nt] = v; per_cu_lds[nt] = lds;
         }
-        const int per_cu = per_cu_cache[nt];
-        const int grid = a.resident ? min(a.n_groups, per_cu * g3_slots()) : a.n_groups;
-        void* kargs[] = {(void*)&a};
-        e = hipLaunchKernel(kern, dim3(grid), dim3(256), kargs, lds, s);
+        e = hipLaunchKernel(kern, dim3(li_heads_grid(a, kern, lds, per_cu_cache[nt], 3)), dim3(256), kargs, lds, s);
         if (e != hipSuccess) return fail(-3, "k_li_heads_mfma launch failed: %s", hipGetErrorString(e));
         SNN_CHECK_LAUNCH("k_li_heads_mfma");
         return 0;
@@ -1680,8 +1712,8 @@ static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, i
                                              : rb == 8 ? k_li_heads<8> : k_li_heads<4>;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(cdiv(M, rb)), dim3(256), lds, s, spk, spk_stride, T, M, Kw,
-                       w_heads_packed, NOp, ldw, col0, NA, NB, kap, out_a, out_b, sum_a, sum_b);
+    hipLaunchKernelGGL(kern, dim3(cdiv(M, rb)), dim3(256), lds, s, c.spk, c.spk_stride, T, M, c.Kw,
+                       c.w, NOp, c.ldw, col0, c.NA, c.NB, kap, out_a, out_b, sum_a, sum_b);
     SNN_CHECK_LAUNCH("k_li_heads");
     return 0;
 }
@@ -1689,24 +1721,16 @@ static int li_heads_cols(const uint32_t* spk, size_t spk_stride, int T, int M, i
 static int li_heads_impl(const uint32_t* spk, size_t spk_stride, int T, int M, int K, const float* w_heads_packed,
                          int NA, int NB, const snn_params* p, float* out_a, float* out_b, float* sum_a, float* sum_b,
                          bool half_split, snn_stream_t s) {
-    if (half_split && !li_heads_reads_split(K, NA, NB)) return fail(-1, "snn_li_heads: split planes need the resident matrix-core kernel");
+    LiHeadsCall c;
+    if (li_heads_call(&c, spk, spk_stride, M, K, w_heads_packed, NA, NB, p, half_split)) return -1;
     if (!spk || !w_heads_packed || !p || !out_a || !out_b || M <= 0 || K <= 0 || NA <= 0 || NB <= 0)
         return fail(-1, "snn_li_heads: bad argument");
     if ((sum_a == nullptr) != (sum_b == nullptr)) return fail(-1, "snn_li_heads: sum_a and sum_b go together");
     if (check_T(T, "snn_li_heads")) return -1;
     Kappa kap;
     li_kappa(p, T, &kap);
-    const int Kw = cdiv(K, 32), ldw = cdiv(NA + NB, 16) * 16;       // columns of a row of the packed matrix
-    // debug / A-B knob: 1 "valu" forces the fp32 VALU kernel, 2 "mfma", 3 "ksplit"; SNN_PRECISION_F32_STRICT always takes the VALU kernel
-    const int force = p->precision == SNN_PRECISION_F32_STRICT ? 1 : knobs().li_heads;
-    // More than 64 outputs per row (num_classes >= 13: 5 K outputs - pascal 24, coco 91 of the reference's configs): one launch per
-    // block of 64 columns (matrix-core kernels; the VALU kernel takes 256); every launch reads all spike planes, which is the small
-    // operand here.  (Until round 4: the VALU kernel up to 256 outputs, an error beyond.)
-    const int step = force == 1 ? 256 : 64;
-    if (half_split && ldw > 64) return fail(-1, "snn_li_heads: split planes need the resident matrix-core kernel");
-    for (int col0 = 0; col0 < ldw; col0 += step) {
-        const int rc = li_heads_cols(spk, spk_stride, T, M, Kw, w_heads_packed, NA, NB, kap, out_a, out_b, sum_a, sum_b, half_split, force,
-                                     ldw, col0, min(step, ldw - col0), (hipStream_t)s);
+    for (int col0 = 0; col0 < c.ldw; col0 += c.step) {
+        const int rc = li_heads_cols(c, T, kap, out_a, out_b, sum_a, sum_b, col0, min(c.step, c.ldw - col0), (hipStream_t)s);
         if (rc) return rc;
     }
     return 0;
@@ -1747,12 +1771,7 @@ static int li_heads_ro_launch(bool ksplit, const LiHeadsArgs& base, const snn_pa
     const void* kern = ksplit ? (const void*)k_li_heads_ksplit_ro<NT, RB, S> : (const void*)k_li_heads_mfma_ro<NT, RB, S>;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    int grid = ksplit ? cdiv(base.M, 16) : base.n_groups;
-    if (!ksplit && base.resident) {                            // persistent work-groups, as k_li_heads_mfma
-        int v = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v <= 0) v = 1;
-        grid = min(base.n_groups, v * g3_slots());
-    }
+    const int grid = ksplit ? cdiv(base.M, 16) : li_heads_grid(base, kern, lds, 0, 1);
     for (int hi = n; hi > 0; hi -= RB) {
         const int lo = max(0, hi - RB);
         LiReadoutArgs ra;
@@ -1775,49 +1794,32 @@ static int li_heads_ro_launch(bool ksplit, const LiHeadsArgs& base, const snn_pa
 static int li_heads_readouts_impl(const uint32_t* spk, size_t spk_stride, const int* steps, int n, int M, int K, const float* w_heads_packed,
                                   int NA, int NB, const snn_params* p, float* out_a, float* out_b, float* sum_a, float* sum_b,
                                   bool half_split, snn_stream_t stream) {
-    if (half_split && !li_heads_reads_split(K, NA, NB)) return fail(-1, "snn_li_heads: split planes need the resident matrix-core kernel");
-    const int Kw = cdiv(K, 32), ldw = cdiv(NA + NB, 16) * 16;
-    const int force = p->precision == SNN_PRECISION_F32_STRICT ? 1 : knobs().li_heads;
-    const int step = force == 1 ? 256 : 64;
+    LiHeadsCall c;
+    if (li_heads_call(&c, spk, spk_stride, M, K, w_heads_packed, NA, NB, p, half_split)) return -1;
     const unsigned long long st_a = (unsigned long long)M * NA, st_b = (unsigned long long)M * NB;
     hipStream_t s = (hipStream_t)stream;
-    for (int col0 = 0; col0 < ldw; col0 += step) {
-        const int NOp = min(step, ldw - col0), nt = NOp / 16;
-        const int kind = li_heads_kind(Kw, NOp, force);
+    // by column tiles and time sums
+    static int (*const ro_launch[4][2])(bool, const LiHeadsArgs&, const snn_params*, const int*, int, unsigned long long, unsigned long long, size_t,
+                                        hipStream_t) = {{li_heads_ro_launch<1, false>, li_heads_ro_launch<1, true>},
+                                                        {li_heads_ro_launch<2, false>, li_heads_ro_launch<2, true>},
+                                                        {li_heads_ro_launch<3, false>, li_heads_ro_launch<3, true>},
+                                                        {li_heads_ro_launch<4, false>, li_heads_ro_launch<4, true>}};
+    for (int col0 = 0; col0 < c.ldw; col0 += c.step) {
+        const int NOp = min(c.step, c.ldw - col0);
+        const int kind = li_heads_kind(c.Kw, NOp, c.force);
         if (kind == 1) {                                       // the fp32 VALU kernel (f32_strict): one launch per readout
             for (int j = 0; j < n; ++j) {
                 Kappa kap;
                 li_kappa(p, steps[j], &kap);
-                const int rc = li_heads_cols(spk, spk_stride, steps[j], M, Kw, w_heads_packed, NA, NB, kap, out_a + j * st_a, out_b + j * st_b,
-                                             sum_a ? sum_a + j * st_a : nullptr, sum_b ? sum_b + j * st_b : nullptr, half_split, force,
-                                             ldw, col0, NOp, s);
+                const int rc = li_heads_cols(c, steps[j], kap, out_a + j * st_a, out_b + j * st_b, sum_a ? sum_a + j * st_a : nullptr,
+                                             sum_b ? sum_b + j * st_b : nullptr, col0, NOp, s);
                 if (rc) return rc;
             }
             continue;
         }
         LiHeadsArgs a;
-        memset(&a, 0, sizeof(a));
-        a.spk = spk; a.spk_stride = spk_stride; a.wT = w_heads_packed; a.out_a = out_a; a.out_b = out_b;
-        a.sum_a = sum_a; a.sum_b = sum_b; a.M = M; a.Kw = Kw; a.NOp = NOp; a.NA = NA; a.NB = NB; a.ldw = ldw; a.col0 = col0;
-        size_t lds;
-        if (kind == 3) {
-            lds = G3_LUT_BYTES + (size_t)4 * 2 * nt * 64 * 16;
-        } else {
-            a.n_groups = cdiv(M, 64);
-            a.half_split = half_split;
-            const size_t all = (size_t)Kw * 3 * NOp * 64;
-            a.resident = all <= 96 * 1024;
-            lds = G3_LUT_BYTES + (a.resident ? all : (size_t)2 * 3 * NOp * 64);
-        }
-        const bool ks = kind == 3;
-        const bool S = sum_a != nullptr;
-        int rc;
-        switch (nt) {
-            case 1: rc = S ? li_heads_ro_launch<1, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<1, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
-            case 2: rc = S ? li_heads_ro_launch<2, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<2, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
-            case 3: rc = S ? li_heads_ro_launch<3, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<3, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
-            default: rc = S ? li_heads_ro_launch<4, true>(ks, a, p, steps, n, st_a, st_b, lds, s) : li_heads_ro_launch<4, false>(ks, a, p, steps, n, st_a, st_b, lds, s); break;
-        }
+        const size_t lds = li_heads_plan(kind, c, out_a, out_b, sum_a, sum_b, col0, NOp, &a);
+        const int rc = ro_launch[NOp / 16 - 1][sum_a != nullptr](kind == 3, a, p, steps, n, st_a, st_b, lds, s);
         if (rc) return rc;
     }
     return 0;

@@ -50,6 +50,35 @@ def test_readout_kernels_equal_single_readout_heads(K, NA, NB, T, M, prec, sums)
                 assert torch.equal(a[j], b), (steps, Tp)
 
 
+@pytest.mark.parametrize("form,K,NA,NB,T,M", [
+    ("mfma", 1024, 9, 36, 12, 45),         # k_li_heads_mfma_ro with W streamed (288 KB of planes), NT = 3
+    ("ksplit", 256, 3, 12, 24, 45),        # k_li_heads_ksplit_ro by force, NT = 1: groups of 16 steps, two of them
+    ("ksplit", 128, 5, 20, 5, 17),         # four words per row: one chunk per wave; last group of 4 accumulator steps, tn odd
+])
+@pytest.mark.parametrize("sums", [False, True])
+def test_readout_kernels_forced_forms_equal_single_readout_heads(monkeypatch, form, K, NA, NB, T, M, sums):
+    """the readout kernels where only SNN_LI_HEADS takes them (the streamed matrix-core loop, the reduction-split form on shapes whose W
+    fits LDS): every readout against the single-readout heads of the same forced form on the first T' planes, bit for bit"""
+    monkeypatch.setenv("SNN_LI_HEADS", form)
+    g = torch.Generator().manual_seed(K + NA + T + M)
+    planes = torch.randint(-2 ** 31, 2 ** 31, (T, M, K // 32), generator=g, dtype=torch.int64).to(torch.int32)
+    planes &= torch.randint(-2 ** 31, 2 ** 31, planes.shape, generator=g, dtype=torch.int64).to(torch.int32)   # ~25 % density
+    planes = planes.to(DEV)
+    wa = (torch.randn(NA, K, generator=g) * 0.02).to(DEV)
+    wb = (torch.randn(NB, K, generator=g) * 0.02).to(DEV)
+    wp = ops.pack_heads(wa, wb)
+    _, p = _params("bf16x3")
+    steps = tuple(range(1, T + 1))
+    got = ops.li_heads_readouts(planes, K, wp, NA, NB, p, steps, want_sums=sums)
+    for j, Tp in enumerate(steps):
+        exp = ops.li_heads(planes[:Tp].contiguous(), K, wp, NA, NB, p, want_sums=sums)
+        for a, b in zip(got, exp):
+            assert torch.equal(a[j], b), Tp
+    for a in got:                                                   # not vacuous: no readout is all zero, and the readouts differ
+        assert all(bool(a[j].any()) for j in range(T))
+        assert any(not torch.equal(a[0], a[j]) for j in range(1, T))
+
+
 def _rpn_module(spec, prec):
     feats, w_s, w_c, w_b = FX.rpn_inputs(spec)
     m = S.RPNHeadSNN(spec["C"], spec["A"], spec["T"]).to(DEV)
