@@ -407,6 +407,61 @@ int snn_spike_conv3x3_bf16x3(const uint32_t* enc, size_t enc_stride_words, const
                              int n_levels, int C_in, int C_out, int T, const uint16_t* w_packed, float* cur,
                              int ldo, snn_stream_t stream);
 
+/* ---- half-precision feature maps: fp16 / bf16 features straight into both heads --------------------------------------------------------
+ * The *_typed twins of the entry points that READ features take them as `const void*` plus a feat_dtype.  A feature element of dtype
+ * SNN_FEAT_F16 / SNN_FEAT_BF16 means its exact fp32 value (both widenings are exact: subnormals, +-0, +-inf and NaN included): the encoder
+ * kernels load the 16-bit element and widen it in registers; neuron arithmetic, RoIAlign interpolation, thresholds and every output stay
+ * fp32, and the call returns bit for bit what the fp32 entry returns for the widened tensor.  (This is NOT fp16 arithmetic: nothing is
+ * computed in half precision.)  With SNN_FEAT_F32 a typed entry IS the fp32 entry - the same launches - and the entries without the
+ * suffix are one-line calls of it.
+ *   - struct layouts are unchanged: the `feat` members of snn_rpn_level / snn_roi_level then point at 16-bit elements;
+ *   - alignment: a half-precision feature base pointer (x, every level's feat) must be 16-byte aligned, else -1 (fp32 pointers: as
+ *     before); inside the kernels no load is wider than the element address guarantees (RoIAlign's x-adjacent tap pairs are two
+ *     2-byte loads: an element address is only 2-byte aligned where W or y W + x is odd);
+ *   - workspace sizes do not depend on the feature dtype;
+ *   - typed kernels exist for the encoders the default plans launch (all levels of the RPN head; the fused RoIAlign encoders on
+ *     word-major planes; the row encoders on word-major planes).  Where the launch plan of the call picks another encoder kernel
+ *     (knob-selected legacy kernels such as SNN_ROI_TAB=0, row-major planes: SNN_PRECISION_F32 / SNN_PLANES=rm detector heads,
+ *     D % 32 != 0) a typed entry with half features returns SNN_STATUS_NO_TYPED_KERNEL (> 0: not an error, snn_last_error is not set) and
+ *     enqueues NOTHING; the caller widens the features to fp32 and calls again with SNN_FEAT_F32. */
+enum { SNN_FEAT_F32 = 0, SNN_FEAT_F16 = 1, SNN_FEAT_BF16 = 2 };
+#define SNN_STATUS_NO_TYPED_KERNEL 1
+int snn_rpn_head_forward_stages_typed(const snn_rpn_level* levels_host, int feat_dtype, int n_levels, int C, int A, int T,
+                                      const snn_params* p_host, const void* w_shared_packed, const float* w_heads_packed,
+                                      float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                      float* sum_bbox, void* workspace, size_t workspace_bytes, int stage_mask, snn_stream_t stream);
+int snn_rpn_head_forward_readouts_typed(const snn_rpn_level* levels_host, int feat_dtype, int n_levels, int C, int A, const int* steps,
+                                        int n_steps, const snn_params* p_host, const void* w_shared_packed, const float* w_heads_packed,
+                                        float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                        float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+int snn_det_head_forward_k_typed(const void* x, int feat_dtype, int R, int D, int Hd, int K, int K4, int T, const snn_params* p_host,
+                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls,
+                                 float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+int snn_det_head_forward_readouts_typed(const void* x, int feat_dtype, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps,
+                                        const snn_params* p_host, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                        const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                        uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* workspace, size_t workspace_bytes,
+                                        snn_stream_t stream);
+int snn_det_head_forward_roialign_k_typed(const snn_roi_level* levels_host, int feat_dtype, int n_levels, int C, const float* rois,
+                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                          const snn_params* p_host, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* workspace,
+                                          size_t workspace_bytes, snn_stream_t stream);
+int snn_det_head_forward_roialign_readouts_typed(const snn_roi_level* levels_host, int feat_dtype, int n_levels, int C, const float* rois,
+                                                 const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4,
+                                                 const int* steps, int n_steps, const snn_params* p_host, const void* w6_packed,
+                                                 int w6_inner, const void* w7_packed, const float* w_heads_packed, float* out_cls,
+                                                 float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls,
+                                                 float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+/* the two stage-level calls the tests compare planes through */
+int snn_encode_nchw_typed(const void* feat, int feat_dtype, int N, int C, int H, int W, int T, const snn_params* p_host,
+                          uint32_t* planes, size_t plane_stride_words, snn_stream_t stream);
+int snn_roi_align_encode_typed(const snn_roi_level* levels_host, int feat_dtype, int n_levels, int C, const float* rois,
+                               const int* roi_batch, const int* roi_level, int R, int T, const snn_params* p_host, uint32_t* planes,
+                               size_t plane_stride_words, float* pooled_dbg, snn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ c_stream = C.c_void_p
 
 SNN_MAX_LEVELS = 8
 SNN_MAX_STEPS = 32
+FEAT_DTYPES = {"f32": 0, "f16": 1, "bf16": 2}          # SNN_FEAT_*
+NO_TYPED_KERNEL = 1                                       # SNN_STATUS_NO_TYPED_KERNEL: nothing was enqueued; widen and call with "f32"
 PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3, "bf16": 4}
 
 
@@ -148,6 +150,26 @@ SYMBOLS = {
                                          C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
     "snn_spike_conv3x3_bf16x3": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_int, c_stream]),
+    # the typed twins (half-precision features): the untyped signature with an int feat_dtype behind the feature argument
+    "snn_rpn_head_forward_stages_typed": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(snn_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                    c_stream]),
+    "snn_rpn_head_forward_readouts_typed": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                      C.POINTER(snn_params)] + [C.c_void_p] * 8 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_k_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +
+                                     [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_readouts_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.POINTER(snn_params),
+                                                      C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_roialign_k_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p] + [C.c_int] * 5 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +
+                                              [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_det_head_forward_roialign_readouts_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.POINTER(snn_params),
+                                                               C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    "snn_encode_nchw_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(snn_params), C.c_void_p, C.c_size_t, c_stream]),
+    "snn_roi_align_encode_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
 }
 
 _LIB = None
@@ -183,6 +205,8 @@ def load(build_if_missing: bool = True):
                           "there is no CPU fallback" % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
+        if path != _build.LIB_PATH and name.endswith("_typed") and not hasattr(lib, name):
+            continue                     # an A/B library from before the typed entry points: fp32 features only (half features: AttributeError)
         fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

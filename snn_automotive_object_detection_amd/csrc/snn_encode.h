@@ -3,6 +3,20 @@
 #pragma once
 
 // ------------------------------------------------------------------------------------------------
+// Half-precision feature elements (SNN_FEAT_F16 / SNN_FEAT_BF16, include/snn_hip.h).  A half element MEANS its exact fp32 value: it is
+// loaded as 16 bits and widened in registers - fp16 by the hardware conversion (subnormals kept), bf16 by a 16-bit shift - and from there
+// the encoders run their fp32 text.  The typed kernels are symbols of their own (k_*_h): the fp32 kernels keep their names and their
+// instruction streams (profiles/half_features_symbol_diff.txt).
+// ------------------------------------------------------------------------------------------------
+struct feat_f16 { uint16_t u; };
+struct feat_bf16 { uint16_t u; };
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float feat_widen(float x) { return x; }
+__device__ __forceinline__ float feat_widen(feat_f16 h) { return (float)__builtin_bit_cast(_Float16, h.u); }
+__device__ __forceinline__ float feat_widen(feat_bf16 h) { return __uint_as_float((uint32_t)h.u << 16); }
+template <typename FT> __device__ __forceinline__ float feat_widen_bits(uint32_t bits16) { FT h; h.u = (uint16_t)bits16; return feat_widen(h); }
+
+// ------------------------------------------------------------------------------------------------
 // K1a: constant-current LIF encoder, NCHW fp32 -> bit-planes [T][N*HW][Cw]
 // Block = 64 positions x 4 channel words; thread = one position x 32 channels, a wave = 64 consecutive positions of one channel
 // word (every load instruction reads one 256-byte run of a channel plane; round 2's 32 x 8 shape read two 128-byte segments of
@@ -20,8 +34,8 @@
 // planes e_n, n > nd, leave COMPRESSED - the four dwords per (row, 64 k) k_compress_planes would make of them (primary occupancy, index
 // halves, secondary occupancy), computed from the block's words while they are in LDS - and their raw words are not written at all:
 // one launch and a 32-MB write + 32-MB read less per head (k_compress_planes stays for the stage-level entry points and the linear layers).
-template <int EM>
-__device__ __forceinline__ void encode_block(const float* __restrict__ feat, int C, int HW, int Cw, int T, const NeuronP& p,
+template <int EM, typename FT>
+__device__ __forceinline__ void encode_block(const FT* __restrict__ feat, int C, int HW, int Cw, int T, const NeuronP& p,
                                              const EncTh& eth, uint32_t* __restrict__ planes, size_t plane_stride, int n, int bx, int by,
                                              int Wpad = 0, size_t wm_rows = 0, uint32_t* __restrict__ cmp = nullptr, int nd = 0) {
     constexpr bool ZR = EM != ENC_GENERIC;
@@ -38,17 +52,17 @@ __device__ __forceinline__ void encode_block(const float* __restrict__ feat, int
         // all 32 channels of the word exist (wave-uniform: a wave is one channel word): 32 plain loads off ONE address - the per-channel
         // predicate cost 14 instructions per load, as many as the encoder steps themselves (round 5: the launch was VALU-bound at 62 % of
         // the HBM rate).  Lanes past the level's last position read its last position; their words are never stored
-        const float* src = feat + ((size_t)n * C + cg * 32) * HW + min(pos, HW - 1);
+        const FT* src = feat + ((size_t)n * C + cg * 32) * HW + min(pos, HW - 1);
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
-            x[j] = src[(size_t)j * HW];
+            x[j] = feat_widen(src[(size_t)j * HW]);
             v[j] = 0.0f;                          // rpn.py:93  v = zeros
         }
     } else {
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
             const int c = cg * 32 + j;
-            x[j] = (pos < HW && c < C) ? feat[((size_t)n * C + c) * HW + pos] : 0.0f;
+            x[j] = (pos < HW && c < C) ? feat_widen(feat[((size_t)n * C + c) * HW + pos]) : 0.0f;
             v[j] = 0.0f;
         }
     }
@@ -134,6 +148,14 @@ __global__ __launch_bounds__(256) void k_encode_nchw(const float* __restrict__ f
     encode_block<EM>(feat, C, HW, Cw, T, p, eth, planes, plane_stride, blockIdx.z, blockIdx.x, blockIdx.y);
 }
 
+// (half-precision features: a wave's 64 consecutive positions are a 128-byte run per load instruction)
+template <int EM, typename FT>
+__global__ __launch_bounds__(256) void k_encode_nchw_h(const FT* __restrict__ feat, int C, int HW, int Cw,
+                                                       int T, NeuronP p, const EncTh eth, uint32_t* __restrict__ planes,
+                                                       size_t plane_stride) {
+    encode_block<EM>(feat, C, HW, Cw, T, p, eth, planes, plane_stride, blockIdx.z, blockIdx.x, blockIdx.y);
+}
+
 // all pyramid levels of the RPN head in one launch (the small levels are launch-latency bound on their own)
 struct EncLevels {
     const float* feat[SNN_MAX_LEVELS];
@@ -152,6 +174,17 @@ __global__ __launch_bounds__(256) void k_encode_levels(const EncLevels lv, int C
     const int local = blockIdx.x - lv.blk_base[l];
     encode_block<EM>(lv.feat[l], C, lv.HW[l], Cw, T, p, eth, planes + (size_t)lv.pos_base[l] * (wm_rows ? 1 : Cw), plane_stride,
                      local / lv.bpi[l], local % lv.bpi[l], blockIdx.y, lv.Wpad[l], wm_rows, cmp ? cmp + lv.pos_base[l] : nullptr, nd);
+}
+
+template <int EM, typename FT>                     // (lv.feat[l] points at FT elements)
+__global__ __launch_bounds__(256) void k_encode_levels_h(const EncLevels lv, int C, int Cw, int T, NeuronP p, const EncTh eth,
+                                                         uint32_t* __restrict__ planes, size_t plane_stride, size_t wm_rows,
+                                                         uint32_t* __restrict__ cmp, int nd) {
+    int l = 0;
+    while (l + 1 < lv.n_levels && (int)blockIdx.x >= lv.blk_base[l + 1]) ++l;
+    const int local = blockIdx.x - lv.blk_base[l];
+    encode_block<EM>(reinterpret_cast<const FT*>(lv.feat[l]), C, lv.HW[l], Cw, T, p, eth, planes + (size_t)lv.pos_base[l] * (wm_rows ? 1 : Cw),
+                     plane_stride, local / lv.bpi[l], local % lv.bpi[l], blockIdx.y, lv.Wpad[l], wm_rows, cmp ? cmp + lv.pos_base[l] : nullptr, nd);
 }
 
 // K1b: encoder on row-major x[R][D] -> bit-planes [T][R][Dw]; a wave covers 64 consecutive reduction indices per
@@ -244,6 +277,7 @@ __global__ __launch_bounds__(256) void k_encode_rows_w(const float* __restrict__
 // K1b'': the same encoder writing WORD-MAJOR planes [T][Dw][R] (what the linear-layer kernels stream best): a work-group takes
 // 32 rows x 8 words (32 x 1 KB of x, 16-byte coalesced loads through LDS), thread = (row tid & 31, word tid >> 5), so the 32
 // lanes of a half-wave store 32 consecutive rows of one word plane: 128-byte runs.  D % 32 == 0, x 16-byte aligned.
+// (typed twin for fp16 / bf16 rows: encode_rows_wm_block / k_encode_rows_wm_h below - a fix here belongs there as well)
 #define ENC_WM_PITCH 260
 template <int EM>
 __global__ __launch_bounds__(256) void k_encode_rows_wm(const float* __restrict__ x, int R, int D, int T, NeuronP p, const EncTh eth,
@@ -289,6 +323,62 @@ __global__ __launch_bounds__(256) void k_encode_rows_wm(const float* __restrict_
     }
 }
 
+// the same text for half-precision rows (a symbol of its own: sharing one __device__ body between the two re-scheduled the fp32 kernel).
+// The load phase differs: 16-byte pieces of eight halves, widened on the way into LDS; x 16-byte aligned as well.
+template <int EM, typename FT>
+__device__ __forceinline__ void encode_rows_wm_block(const FT* __restrict__ x, int R, int D, int T, const NeuronP& p, const EncTh& eth,
+                                                     uint32_t* __restrict__ planes, size_t plane_stride) {
+    constexpr bool ZR = EM != ENC_GENERIC;
+    __shared__ __attribute__((aligned(16))) float tile[32 * ENC_WM_PITCH];
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.y * 32, w0 = blockIdx.x * 8;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = tid + 256 * j;                            // 16-byte piece: row q / 32, halves 8 (q % 32) .. of the 256-element run, widened on the way into LDS
+        const int row = q >> 5, col = w0 * 32 + (q & 31) * 8;
+        u32x4 h = {0u, 0u, 0u, 0u};
+        if (r0 + row < R && col < D) h = *reinterpret_cast<const u32x4*>(x + (size_t)(r0 + row) * D + col);
+        float* d = tile + row * ENC_WM_PITCH + (q & 31) * 8;
+        const f32x4 lo = {feat_widen_bits<FT>(h.x & 0xffffu), feat_widen_bits<FT>(h.x >> 16), feat_widen_bits<FT>(h.y & 0xffffu), feat_widen_bits<FT>(h.y >> 16)};
+        const f32x4 hi = {feat_widen_bits<FT>(h.z & 0xffffu), feat_widen_bits<FT>(h.z >> 16), feat_widen_bits<FT>(h.w & 0xffffu), feat_widen_bits<FT>(h.w >> 16)};
+        *reinterpret_cast<f32x4*>(d) = lo;
+        *reinterpret_cast<f32x4*>(d + 4) = hi;
+    }
+    __syncthreads();
+    const int row = tid & 31, wd = tid >> 5;
+    if (r0 + row >= R || (w0 + wd) * 32 >= D) return;
+    float xv[32], v[32];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const f32x4 t4 = *reinterpret_cast<const f32x4*>(tile + row * ENC_WM_PITCH + wd * 32 + 4 * q);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { xv[4 * q + r] = t4[r]; v[4 * q + r] = 0.0f; }      // v = 0: faster_rcnn.py:484
+    }
+    uint32_t* dst = planes + (size_t)(w0 + wd) * R + r0 + row;
+    uint32_t prev = 0;
+    for (int t = 0; t < T; ++t) {
+        uint32_t word = 0;
+        if (EM == ENC_QUANT) {                      // period planes by thresholds (snn_common.h)
+            const float th = eth.th[t];
+#pragma unroll
+            for (int b = 31; b >= 0; --b) enc_quant_word(xv[b], th, word);
+            const uint32_t cum = word;
+            word = cum & ~prev;
+            prev = cum;
+        } else {
+#pragma unroll
+            for (int b = 31; b >= 0; --b) enc_step_word<ZR>(xv[b], v[b], p, word);          // bit 31 first
+        }
+        dst[(size_t)t * plane_stride] = word;
+    }
+}
+
+template <int EM, typename FT>
+__global__ __launch_bounds__(256) void k_encode_rows_wm_h(const FT* __restrict__ x, int R, int D, int T, NeuronP p, const EncTh eth,
+                                                          uint32_t* __restrict__ planes, size_t plane_stride) {
+    encode_rows_wm_block<EM>(x, R, D, T, p, eth, planes, plane_stride);
+}
+
 // K1d (round 5): the detector's encoder for the structured-sparse fc6 in ONE launch - period planes by thresholds, written straight in
 // fc6's reduction order k' = bin * C + channel (what k_permute_planes made of the reference-order planes) and, for the planes e_3 ..,
 // COMPRESSED (what k_compress_planes made of those): three launches and two HBM round trips of the planes become one.
@@ -297,6 +387,7 @@ __global__ __launch_bounds__(256) void k_encode_rows_wm(const float* __restrict_
 // tasks, lane = bin (S of 64 lanes), the lane's 32 channels are 32 loads at stride S floats - every load instruction reads one S-float run of
 // the RoI's row - and the T words go to LDS [t][cb][RoI][bin] (odd pitch S: conflict-free both ways).  Store: thread = (RoI, item): the dense planes' words as they are, a sparse
 // plane's pair through sp_compress_pair - runs of ENCP_RB consecutive RoIs of one word plane / array.
+// (typed twin for fp16 / bf16 rows: encode_rows_perm_block / k_encode_rows_perm_h below - a fix here belongs there as well)
 #define ENCP_LDS_WORDS 19200                        // planes per pass through LDS: 19200 / (2 S RB) - 12 at RB = 16, 24 at RB = 8 (75 KB); longer windows take more passes
 template <int S, int RB, int NW>                    // NW waves per block (4 or 8: 2 RB tasks over NW waves, two at a time)
 __global__ __launch_bounds__(64 * NW) void k_encode_rows_perm(const float* __restrict__ x, int R, int C, int T, int nd, const EncTh eth,
@@ -381,6 +472,85 @@ __global__ __launch_bounds__(64 * NW) void k_encode_rows_perm(const float* __res
             }
         }
     }
+}
+
+// the same text for half-precision rows (a symbol of its own, as above): a lane's 32 loads are 2-byte elements at stride S
+template <int S, int RB, int NW, typename FT>
+__device__ __forceinline__ void encode_rows_perm_block(const FT* __restrict__ x, int R, int C, int T, int nd, const EncTh& eth,
+                                                       uint32_t* __restrict__ planes, uint32_t* __restrict__ cmp) {
+    static_assert(S <= 64, "one lane per bin");
+    extern __shared__ uint32_t pw[];                          // [min(T, TMAX)][2][RB][S]
+    constexpr int TMAX = ENCP_LDS_WORDS / (2 * S * RB);
+    static_assert((2 * RB) % (2 * NW) == 0, "tasks two at a time per wave");
+    __shared__ uint16_t code[256];
+    if (threadIdx.x < 256) code[threadIdx.x] = sp_byte_code(threadIdx.x);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r0 = blockIdx.x * RB, cp = blockIdx.y, cbn = C / 32, D = C * S, Dw = D / 32;
+    const size_t plane_words = (size_t)Dw * R, cmp_plane = (size_t)(Dw / 2) * SP_A_ARR * R;
+    for (int t0 = 0; t0 < T; t0 += TMAX) {
+        const int tn = min(TMAX, T - t0);
+        if (t0) __syncthreads();
+        // ---- encode: tasks (RoI, cb) over the waves; the next task's 32 loads are in flight while this one's words are formed
+        auto load_task = [&](float (&xv)[32], const int task) __attribute__((always_inline)) {
+            const int row = r0 + (task >> 1), cb = task & 1;
+            const FT* src = x + (size_t)min(row, R - 1) * D + (size_t)((2 * cp + cb) * 32) * S + min(lane, S - 1);
+#pragma unroll
+            for (int j = 0; j < 32; ++j) xv[j] = feat_widen(src[j * S]);
+        };
+        auto encode_task = [&](const float (&xv)[32], const int task) __attribute__((always_inline)) {
+            const int rl = task >> 1, cb = task & 1;
+            if (lane < S) {
+                uint32_t prev = 0;
+                for (int t = 0; t < t0 + tn; ++t) {          // (cumulative words from step 0: a later pass re-derives what it needs)
+                    uint32_t word = 0;
+                    const float th = eth.th[t];
+#pragma unroll
+                    for (int j = 31; j >= 0; --j) enc_quant_word(xv[j], th, word);
+                    const uint32_t cum = word;
+                    word = cum & ~prev;
+                    prev = cum;
+                    if (t >= t0) pw[(((t - t0) * 2 + cb) * RB + rl) * S + lane] = word;
+                }
+            }
+        };
+        float xa[32], xb[32];
+        load_task(xa, wave);
+#pragma unroll 1
+        for (int task = wave; task < 2 * RB; task += 2 * NW) {     // (2 RB / NW tasks per wave: even)
+            load_task(xb, task + NW);
+            encode_task(xa, task);
+            if (task + 2 * NW < 2 * RB) load_task(xa, task + 2 * NW);
+            encode_task(xb, task + NW);
+        }
+        __syncthreads();
+        // ---- store: thread = (RoI tid % RB, item tid / RB)
+        const int rl = tid & (RB - 1), row = r0 + rl;                    // (RB = 8 or 16)
+        if (row < R) {
+            for (int t = t0; t < t0 + tn; ++t) {
+                const uint32_t* pt = pw + (size_t)(t - t0) * 2 * S * RB;
+                if (t < nd || !cmp) {                         // raw words (bin, cb) -> word plane bin * cbn + 2 cp + cb
+                    for (int it = tid / RB; it < 2 * S; it += 64 * NW / RB) {
+                        const int cb = it / S, bin = it % S;
+                        planes[(size_t)t * plane_words + (size_t)(bin * cbn + 2 * cp + cb) * R + row] = pt[(cb * RB + rl) * S + bin];
+                    }
+                } else {                                      // compressed step (bin, cp): pair index (bin * cbn + 2 cp) / 2
+                    for (int bin = tid / RB; bin < S; bin += 64 * NW / RB) {
+                        uint32_t c4[4];
+                        sp_compress_pair(pt[rl * S + bin], pt[(RB + rl) * S + bin], code, c4);
+                        uint32_t* o = cmp + (size_t)(t - nd) * cmp_plane + (size_t)(bin * (cbn / 2) + cp) * SP_A_ARR * R + row;
+#pragma unroll
+                        for (int j = 0; j < SP_A_ARR; ++j) o[(size_t)j * R] = c4[j];
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int S, int RB, int NW, typename FT>
+__global__ __launch_bounds__(64 * NW) void k_encode_rows_perm_h(const FT* __restrict__ x, int R, int C, int T, int nd, const EncTh eth,
+                                                            uint32_t* __restrict__ planes, uint32_t* __restrict__ cmp) {
+    encode_rows_perm_block<S, RB, NW>(x, R, C, T, nd, eth, planes, cmp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -532,6 +702,7 @@ __global__ __launch_bounds__(256) void k_roi_align_encode_wm(const RoiArgs a) {
 // wave), and with the plain block order by L2 misses as well - 1.2 GB fetched for 200 MB of feature maps, since every XCD
 // saw every channel plane.  The XCD-aware, channel-major block order below brings that to 0.34 GB (77 % L2 hits).
 // Needs W >= 2 on every level and C*H*W < 2^29 elements per image (32-bit element offsets); the launcher checks.
+// (typed twin for fp16 / bf16 maps: roi_align_encode_tab_block / k_roi_align_encode_tab_h below - a fix here belongs there as well)
 struct __attribute__((aligned(16))) RoiTabEntry { int a, b; float l, h; };
 __global__ __launch_bounds__(256) void k_roi_align_encode_tab(const RoiArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t wbuf_dyn[];          // [t][2E words][4 RW RoIs]
@@ -646,6 +817,130 @@ __global__ __launch_bounds__(256) void k_roi_align_encode_tab(const RoiArgs a) {
     }
 }
 
+// the same text for half-precision maps (a symbol of its own, as for the row encoders; a.lv[].feat points at FT elements).  The two
+// x-adjacent taps of a sample row: an element address is only 2-byte aligned (odd W, odd y W + x), so the pair is two 2-byte loads - never a
+// load wider than the address guarantees
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+template <typename FT>
+__device__ __forceinline__ f32x2u roi_tap_pair(const FT* __restrict__ f) {
+    f32x2u r;
+    r.x = feat_widen(f[0]); r.y = feat_widen(f[1]);
+    return r;
+}
+template <typename FT>
+__device__ __forceinline__ void roi_align_encode_tab_block(const RoiArgs& a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t wbuf_dyn[];          // [t][2E words][4 RW RoIs]
+    __shared__ RoiTabEntry tab[4][32];                                           // per wave: 0..13 rows, 16..29 columns
+    const int D = a.C * 49, E = a.E;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // work-group -> (element block, RoI group), XCD-aware and channel-major in time: work-group b runs on XCD b % 8, so XCD x takes
+    // the element blocks x, x + 8, ... and for each of them ALL RoI groups, one block after the other - at any moment an XCD's
+    // work-groups read a handful of channel planes (which its 4-MB L2 holds) instead of all of them (a.n_rg RoI groups)
+    const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
+    const int eblk = (jj / a.n_rg) * 8 + xcd, rgrp = jj % a.n_rg;
+    if (eblk * E * 2 >= a.Dw) return;
+    const int RW = a.RW, RG = 4 * RW;                          // RoIs per wave / per work-group
+    const int r0 = rgrp * RG;
+    const int d0 = eblk * E * 64;
+    RoiTabEntry* const tb = tab[wave];
+    for (int i = 0; i < RW; ++i) {
+        const int rl = wave * RW + i, r = r0 + rl;               // wave-uniform
+        if (r >= a.R) break;
+        const RoiLevel L = a.lv[a.roi_level[r]];
+        const float* roi = a.rois + (size_t)r * 4;
+        const FT* const fimg = reinterpret_cast<const FT*>(L.feat) + (size_t)a.roi_batch[r] * a.C * (size_t)(L.H * L.W);
+        const int HW = L.H * L.W;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                   // the previous RoI's lookups are done
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 32 && (lane & 15) < 14) {
+            // lane 0..13: sample row s = 2 ph + iy;  lane 16..29: sample column s = 2 pw + ix
+            const bool is_x = lane >= 16;
+            const int sidx = lane & 15, pb = sidx >> 1, ii = sidx & 1;
+            const float lo = __fmul_rn(is_x ? roi[0] : roi[1], L.scale);
+            const float ext = fmaxf(__fsub_rn(__fmul_rn(is_x ? roi[2] : roi[3], L.scale), lo), 1.0f);
+            const float bin = __fdiv_rn(ext, 7.0f);
+            const float b0 = __fadd_rn(lo, __fmul_rn((float)pb, bin));
+            float y = __fadd_rn(b0, __fdiv_rn(__fmul_rn((float)ii + 0.5f, bin), 2.0f));
+            const int n = is_x ? L.W : L.H;
+            RoiTabEntry e;
+            if (y < -1.0f || y > (float)n) { e.a = 0; e.b = 0; e.l = -1.0f; e.h = 0.0f; }     // outside the map: l < 0, offsets stay valid
+            else {
+                y = fmaxf(y, 0.0f);
+                int y_low = (int)y, y_high;
+                if (y_low >= n - 1) { y_high = y_low = n - 1; y = (float)y_low; } else y_high = y_low + 1;
+                e.l = __fsub_rn(y, (float)y_low);
+                e.h = __fsub_rn(1.0f, e.l);
+                if (is_x) { e.b = y_high == y_low; e.a = e.b ? y_low - 1 : y_low; }      // pair base, clamped
+                else { e.a = y_low * L.W; e.b = y_high * L.W; }
+            }
+            tb[lane] = e;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int eg = 0; eg < E; ++eg) {
+            const int d = d0 + eg * 64 + lane;
+            float val = 0.0f;
+            if (d < D) {
+                const int c = d / 49, bin = d - 49 * c, ph = bin / 7, pw = bin - 7 * ph;
+                const FT* const f = fimg + (unsigned)(c * HW);
+                RoiTabEntry ye[2], xe[2];
+                ye[0] = tb[2 * ph]; ye[1] = tb[2 * ph + 1]; xe[0] = tb[16 + 2 * pw]; xe[1] = tb[16 + 2 * pw + 1];
+                // all eight tap pairs are requested before any is used (samples outside the map read row / column 0 and are dropped)
+                f32x2u pt[2][2], qt[2][2];
+#pragma unroll
+                for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                    for (int ix = 0; ix < 2; ++ix) {
+                        pt[iy][ix] = roi_tap_pair(f + (ye[iy].a + xe[ix].a));
+                        qt[iy][ix] = roi_tap_pair(f + (ye[iy].b + xe[ix].a));
+                    }
+                float s[2][2];
+#pragma unroll
+                for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                    for (int ix = 0; ix < 2; ++ix) {
+                        const bool ok = ye[iy].l >= 0.0f && xe[ix].l >= 0.0f;
+                        const f32x2u p2 = pt[iy][ix], q2 = qt[iy][ix];
+                        const float v1 = xe[ix].b ? p2.y : p2.x, v2 = p2.y, v3 = xe[ix].b ? q2.y : q2.x, v4 = q2.y;
+                        float acc = __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].h), v1);
+                        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].l), v2));
+                        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].h), v3));
+                        acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].l), v4));
+                        s[iy][ix] = ok ? acc : 0.0f;
+                    }
+                val = __fdiv_rn(__fadd_rn(__fadd_rn(__fadd_rn(s[0][0], s[0][1]), s[1][0]), s[1][1]), 4.0f);
+                if (a.pooled) a.pooled[(size_t)r * D + d] = val;
+            }
+            float v = 0.0f;
+            unsigned long long prev = 0ull;
+            for (int t = 0; t < a.T; ++t) {
+                unsigned long long m;
+                if (a.quant) {
+                    const unsigned long long cum = __ballot(d < D && val >= a.eth.th[t]);     // first spike at or before t
+                    m = cum & ~prev;
+                    prev = cum;
+                } else {
+                    bool zz = enc_step(val, v, a.p);
+                    v = (zz && a.p.v_fire != 0.0f) ? a.p.v_fire : v;                           // period planes
+                    m = __ballot(zz && d < D);
+                }
+                if (lane == 0) {
+                    wbuf_dyn[((t * E + eg) * 2 + 0) * RG + rl] = (uint32_t)m;
+                    wbuf_dyn[((t * E + eg) * 2 + 1) * RG + rl] = (uint32_t)(m >> 32);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int w0 = eblk * E * 2;
+    for (int idx = threadIdx.x; idx < a.T * 2 * E * RG; idx += 256) {
+        const int rl = idx % RG, wd = (idx / RG) % (2 * E), t = idx / (2 * E * RG);
+        if (r0 + rl < a.R && w0 + wd < a.Dw)
+            a.planes[(size_t)t * a.plane_stride + (size_t)(w0 + wd) * a.R + r0 + rl] = wbuf_dyn[(t * 2 * E + wd) * RG + rl];
+    }
+}
+template <typename FT>
+__global__ __launch_bounds__(256) void k_roi_align_encode_tab_h(const RoiArgs a) { roi_align_encode_tab_block<FT>(a); }
 
 // K1e (round 6): K1c'' writing what the structured-sparse fc6 reads - period planes in fc6's reduction order k' = bin * C + channel, the planes
 // e_3 .. COMPRESSED - so that the default product path (RoIHeadsSNN.fuse_roi_align) needs neither k_permute_planes nor k_compress_planes nor
@@ -660,6 +955,7 @@ __global__ __launch_bounds__(256) void k_roi_align_encode_tab(const RoiArgs a) {
 // values and planes are bit-identical to K1c'' + k_permute_planes + k_compress_planes (tests/test_gpu_roialign.py compares the workspace bytes).
 // A load instruction touches 8 channel planes x one or two lines of ONE feature row (K1c'': ~28 lines - 7 bin rows of 1.3 channels).
 // Threshold form of the encoder only (a.quant: the launcher falls back to the three launches otherwise); C % 64 == 0.
+// (typed twin for fp16 / bf16 maps: roi_align_encode_perm_block / k_roi_align_encode_perm_h below - a fix here belongs there as well)
 template <int RW>
 __global__ __launch_bounds__(256) void k_roi_align_encode_perm(const RoiArgs a) {
     constexpr int RG = 4 * RW;
@@ -804,3 +1100,150 @@ __global__ __launch_bounds__(256) void k_roi_align_encode_perm(const RoiArgs a) 
         }
     }
 }
+
+// the same text for half-precision maps (a symbol of its own, as above): tap pairs as two 2-byte loads (roi_tap_pair)
+template <int RW, typename FT>
+__device__ __forceinline__ void roi_align_encode_perm_block(const RoiArgs& a) {
+    constexpr int RG = 4 * RW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pbuf[];          // word pairs [t][7][RG] (8 bytes each), then the raw ballots [t][RG][8 octets]
+    unsigned long long* const mbuf = reinterpret_cast<unsigned long long*>(pbuf + (size_t)a.T * 7 * RG * 8);
+    __shared__ RoiTabEntry tab[4][RW][16];                                        // per wave and RoI: 0, 1 = the two sample rows of ph; 2 .. 15 = sample columns
+    __shared__ uint16_t code[256];
+    code[threadIdx.x] = sp_byte_code(threadIdx.x);
+    const int T = a.T;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // work-group -> (channel pair-block cp, RoI group, bin row): XCD b % 8 keeps to ONE cp where the cp count divides 8, and takes the seven bin rows of
+    // a RoI group one after the other (neighbouring bin rows read neighbouring feature rows of the same windows)
+    const int n_cp = a.C / 64, n_items = a.n_rg * 7;
+    int cp, item;
+    if (8 % n_cp == 0) {
+        const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3, per = 8 / n_cp;
+        cp = xcd % n_cp;
+        item = jj * per + xcd / n_cp;
+    } else { cp = blockIdx.x % n_cp; item = blockIdx.x / n_cp; }
+    if (item >= n_items) return;
+    const int rgrp = item / 7, ph = item - 7 * rgrp;
+    const int r0 = rgrp * RG;
+    // lane = channel-of-the-octet * 8 + bin column (7 of 8 used): CONSECUTIVE lanes read neighbouring bins of one channel plane - the first form, with the
+    // channel fastest, put every lane of a quad on another channel plane and cost 0.42 ms against 0.25 for the table kernel (profiles/r6_roi_fold_ab.txt)
+    const int pw = min(lane & 7, 6), ch_l = lane >> 3;
+    const bool act = (lane & 7) < 7;
+    // ---- sample tables of this wave's RoIs (K1c'': same operations, same order)
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int r = r0 + wave * RW + i;                        // wave-uniform
+        if (r >= a.R) break;
+        const RoiLevel L = a.lv[a.roi_level[r]];
+        const float* roi = a.rois + (size_t)r * 4;
+        if (lane < 16) {
+            // lane 0, 1: sample row s = 2 ph + lane;  lane 2 .. 15: sample column s = lane - 2 = 2 pw + ix
+            const bool is_x = lane >= 2;
+            const int sidx = is_x ? lane - 2 : 2 * ph + lane, pb = sidx >> 1, ii = sidx & 1;
+            const float lo = __fmul_rn(is_x ? roi[0] : roi[1], L.scale);
+            const float ext = fmaxf(__fsub_rn(__fmul_rn(is_x ? roi[2] : roi[3], L.scale), lo), 1.0f);
+            const float bin = __fdiv_rn(ext, 7.0f);
+            const float b0 = __fadd_rn(lo, __fmul_rn((float)pb, bin));
+            float y = __fadd_rn(b0, __fdiv_rn(__fmul_rn((float)ii + 0.5f, bin), 2.0f));
+            const int n = is_x ? L.W : L.H;
+            RoiTabEntry e;
+            if (y < -1.0f || y > (float)n) { e.a = 0; e.b = 0; e.l = -1.0f; e.h = 0.0f; }     // outside the map: l < 0, offsets stay valid
+            else {
+                y = fmaxf(y, 0.0f);
+                int y_low = (int)y, y_high;
+                if (y_low >= n - 1) { y_high = y_low = n - 1; y = (float)y_low; } else y_high = y_low + 1;
+                e.l = __fsub_rn(y, (float)y_low);
+                e.h = __fsub_rn(1.0f, e.l);
+                if (is_x) { e.b = y_high == y_low; e.a = e.b ? y_low - 1 : y_low; }      // pair base, clamped
+                else { e.a = y_low * L.W; e.b = y_high * L.W; }
+            }
+            tab[wave][i][lane] = e;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int o = 0; o < 8; ++o) {
+        const int c = cp * 64 + o * 8 + ch_l;
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            const int rl = wave * RW + i, r = r0 + rl;           // wave-uniform
+            if (r >= a.R) break;
+            const RoiLevel L = a.lv[a.roi_level[r]];
+            const int HW = L.H * L.W;
+            const FT* const f = reinterpret_cast<const FT*>(L.feat) + (size_t)a.roi_batch[r] * a.C * (size_t)HW + (unsigned)(c * HW);
+            const RoiTabEntry* const tb = tab[wave][i];
+            RoiTabEntry ye[2], xe[2];
+            ye[0] = tb[0]; ye[1] = tb[1]; xe[0] = tb[2 + 2 * pw]; xe[1] = tb[3 + 2 * pw];
+            // all eight tap pairs are requested before any is used (samples outside the map read row / column 0 and are dropped)
+            f32x2u pt[2][2], qt[2][2];
+#pragma unroll
+            for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                for (int ix = 0; ix < 2; ++ix) {
+                    pt[iy][ix] = roi_tap_pair(f + (ye[iy].a + xe[ix].a));
+                    qt[iy][ix] = roi_tap_pair(f + (ye[iy].b + xe[ix].a));
+                }
+            float sm[2][2];
+#pragma unroll
+            for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                for (int ix = 0; ix < 2; ++ix) {
+                    const bool ok = ye[iy].l >= 0.0f && xe[ix].l >= 0.0f;
+                    const f32x2u p2 = pt[iy][ix], q2 = qt[iy][ix];
+                    const float v1 = xe[ix].b ? p2.y : p2.x, v2 = p2.y, v3 = xe[ix].b ? q2.y : q2.x, v4 = q2.y;
+                    float acc = __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].h), v1);
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].l), v2));
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].h), v3));
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].l), v4));
+                    sm[iy][ix] = ok ? acc : 0.0f;
+                }
+            const float val = __fdiv_rn(__fadd_rn(__fadd_rn(__fadd_rn(sm[0][0], sm[0][1]), sm[1][0]), sm[1][1]), 4.0f);
+            unsigned long long prev = 0ull;
+            unsigned long long* const dst = mbuf + (size_t)rl * 8 + o;
+            for (int t = 0; t < T; ++t) {
+                const unsigned long long cum = __ballot(act && val >= a.eth.th[t]);           // first spike at or before t
+                const unsigned long long m = cum & ~prev;                                      // bit (channel * 8 + bin column): byte c = the bins of channel c
+                prev = cum;
+                if (lane == 0) dst[(size_t)t * (RG * 8)] = m;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- bit transposition by ballot: for a (t, RoI) the 64 bytes of mbuf are the 64 channels' bin bits (byte = octet * 8 + channel of the octet); lane = channel
+    // reads its byte, and the ballot of bit pw over the lanes IS the word pair (channel blocks 2 cp, 2 cp + 1) of bin column pw.  (The first form
+    // transposed every 8 x 8 ballot on the scalar unit inside the task loop - 18 scalar instructions per step and task: 0.34 ms for the launch.)
+    for (int it = wave; it < T * RG; it += 4) {
+        const unsigned int byte = reinterpret_cast<const unsigned char*>(mbuf)[(size_t)it * 64 + lane];
+        const int t = it / RG, rl = it - t * RG;
+        unsigned long long wp = 0ull;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+            const unsigned long long b = __ballot((byte >> q) & 1u);
+            wp = lane == q ? b : wp;
+        }
+        if (lane < 7) *reinterpret_cast<unsigned long long*>(pbuf + ((size_t)(t * 7 + lane) * RG + rl) * 8) = wp;
+    }
+    __syncthreads();
+    // ---- store: item = (t, pw, RoI): the word pair (channel blocks 2 cp, 2 cp + 1) of bin ph * 7 + pw
+    const int cbn = a.C / 32;
+    const size_t R = (size_t)a.R, cmp_plane = (size_t)(a.Dw / 2) * SP_A_ARR * R;
+    for (int idx = threadIdx.x; idx < T * 7 * RG; idx += 256) {
+        const int rl = idx % RG, pwi = (idx / RG) % 7, t = idx / (7 * RG);
+        const size_t row = (size_t)(r0 + rl);
+        if (row >= R) continue;
+        const uint2 w2 = *reinterpret_cast<const uint2*>(pbuf + (size_t)idx * 8);
+        const int bin = ph * 7 + pwi;
+        if (t < a.nd || !a.cmp) {
+            uint32_t* o = a.planes + (size_t)t * a.plane_stride + (size_t)(bin * cbn + 2 * cp) * R + row;
+            o[0] = w2.x; o[R] = w2.y;
+        } else {
+            uint32_t c4[4];
+            sp_compress_pair(w2.x, w2.y, code, c4);
+            uint32_t* o = a.cmp + (size_t)(t - a.nd) * cmp_plane + (size_t)(bin * (cbn / 2) + cp) * SP_A_ARR * R + row;
+#pragma unroll
+            for (int j = 0; j < SP_A_ARR; ++j) o[(size_t)j * R] = c4[j];
+        }
+    }
+}
+template <int RW, typename FT>
+__global__ __launch_bounds__(256) void k_roi_align_encode_perm_h(const RoiArgs a) { roi_align_encode_perm_block<RW, FT>(a); }

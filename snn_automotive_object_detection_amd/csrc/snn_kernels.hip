@@ -509,6 +509,39 @@ __global__ __launch_bounds__(1024) void k_det_payload(const float* __restrict__ 
     if (tid == 0) counts[img] = n;
 }
 
+// ---- launches of the typed (half-precision feature) encoders: the arguments of the fp32 launch next to which each is called, per encoder mode
+template <typename FT>
+static void launch_encode_nchw_h(int em, dim3 g, int T, hipStream_t s, const void* feat, int C, int HW, int Cw, const NeuronP& np, const EncTh& eth,
+                                 uint32_t* planes, size_t plane_stride) {
+    const FT* f = (const FT*)feat;
+    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_nchw_h<ENC_QUANT, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
+    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_nchw_h<ENC_ZR, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
+    else hipLaunchKernelGGL((k_encode_nchw_h<ENC_GENERIC, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
+}
+
+template <typename FT>
+static void launch_encode_rows_wm_h(int em, dim3 g, hipStream_t s, const void* x, int R, int D, int T, const NeuronP& np, const EncTh& eth,
+                                    uint32_t* planes, size_t plane_stride) {
+    const FT* xf = (const FT*)x;
+    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_QUANT, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
+    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_ZR, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
+    else hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_GENERIC, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
+}
+
+template <typename FT>                               // the typed forms of rpn_head_impl's encoder launch (same arguments per encoder mode)
+static void launch_encode_levels_h(int em, dim3 ge, int Tc, hipStream_t s, const EncLevels& el, int C, int Cw, const NeuronP& np, const EncTh& eth,
+                                   uint32_t* enc, size_t enc_stride, size_t wm_rows, uint32_t* enc_cmp) {
+    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_levels_h<ENC_QUANT, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, enc_cmp, 2);
+    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_levels_h<ENC_ZR, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
+    else hipLaunchKernelGGL((k_encode_levels_h<ENC_GENERIC, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
+}
+
+template <typename FT>
+static const void* encode_rows_perm_h_kernel(int rb, int nw) {
+    return rb == 16 ? (nw == 8 ? (const void*)k_encode_rows_perm_h<49, 16, 8, FT> : (const void*)k_encode_rows_perm_h<49, 16, 4, FT>)
+                    : (nw == 8 ? (const void*)k_encode_rows_perm_h<49, 8, 8, FT> : (const void*)k_encode_rows_perm_h<49, 8, 4, FT>);
+}
+
 extern "C" {
 
 int snn_version(void) { return 2; }
@@ -1364,18 +1397,34 @@ static int check_T(int T, const char* who) {
     return 0;
 }
 
+// half-precision features (include/snn_hip.h): a known dtype, and a 16-byte aligned base pointer for the 16-bit types
+static int check_feat(const void* ptr, int fdt, const char* who) {
+    if (fdt != SNN_FEAT_F32 && fdt != SNN_FEAT_F16 && fdt != SNN_FEAT_BF16) return fail(-1, "%s: unknown feat_dtype %d", who, fdt);
+    if (fdt != SNN_FEAT_F32 && ptr && ((uintptr_t)ptr & 15)) return fail(-1, "%s: half-precision features must be 16-byte aligned", who);
+    return 0;
+}
+
 int snn_encode_nchw(const float* feat, int N, int C, int H, int W, int T, const snn_params* p,
                     uint32_t* planes, size_t plane_stride, snn_stream_t s) {
+    return snn_encode_nchw_typed(feat, SNN_FEAT_F32, N, C, H, W, T, p, planes, plane_stride, s);
+}
+
+int snn_encode_nchw_typed(const void* feat_v, int fdt, int N, int C, int H, int W, int T, const snn_params* p,
+                          uint32_t* planes, size_t plane_stride, snn_stream_t s) {
+    const float* feat = (const float*)feat_v;
     if (!feat || !planes || !p || N <= 0 || C <= 0 || H <= 0 || W <= 0)
         return fail(-1, "snn_encode_nchw: bad argument");
     if (check_T(T, "snn_encode_nchw")) return -1;
+    if (check_feat(feat_v, fdt, "snn_encode_nchw")) return -1;
     const int Cw = cdiv(C, 32), HW = H * W;
     NeuronP np = make_p(p, p->v_th_enc);
     if (knobs().stage_periods && enc_zero_rest(np)) np.v_fire = ENC_FIRED;      // (tests / tools: period planes)
     const EncTh* eth;
     const int em = enc_mode(np, &eth);
     const dim3 g(cdiv(HW, ENC_PB), cdiv(Cw, ENC_WB), N);
-    if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_nchw<ENC_QUANT>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
+    if (fdt == SNN_FEAT_F16) launch_encode_nchw_h<feat_f16>(em, g, T, (hipStream_t)s, feat_v, C, HW, Cw, np, *eth, planes, plane_stride);
+    else if (fdt == SNN_FEAT_BF16) launch_encode_nchw_h<feat_bf16>(em, g, T, (hipStream_t)s, feat_v, C, HW, Cw, np, *eth, planes, plane_stride);
+    else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_nchw<ENC_QUANT>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
     else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_nchw<ENC_ZR>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
     else hipLaunchKernelGGL(k_encode_nchw<ENC_GENERIC>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
     SNN_CHECK_LAUNCH("k_encode_nchw");
@@ -1398,11 +1447,14 @@ int snn_affine_act_nchw(const float* x, const float* scale, const float* bias, c
 }
 
 // word-major planes [T][Dw][R] need D % 32 == 0 and 16-byte aligned rows (k_encode_rows_wm)
-static bool encode_rows_wm_ok(const float* x, int D) { return D % 32 == 0 && ((uintptr_t)x & 15) == 0; }
+static bool encode_rows_wm_ok(const void* x, int D) { return D % 32 == 0 && ((uintptr_t)x & 15) == 0; }
 
-static int encode_rows_impl(const float* x, int R, int D, int T, const snn_params* p, uint32_t* planes,
-                            size_t plane_stride, bool wm, snn_stream_t s, bool periods = false) {
+// fdt != SNN_FEAT_F32: x points at 16-bit elements; typed kernels exist for word-major planes only (else SNN_STATUS_NO_TYPED_KERNEL, nothing enqueued)
+static int encode_rows_impl(const void* x_v, int R, int D, int T, const snn_params* p, uint32_t* planes,
+                            size_t plane_stride, bool wm, snn_stream_t s, bool periods = false, int fdt = SNN_FEAT_F32) {
+    const float* x = (const float*)x_v;
     if (!x || !planes || !p || R <= 0 || D <= 0) return fail(-1, "snn_encode_rows: bad argument");
+    if (fdt != SNN_FEAT_F32 && !wm) return SNN_STATUS_NO_TYPED_KERNEL;
     if (check_T(T, "snn_encode_rows")) return -1;
     const int Dw = cdiv(D, 32);
     const size_t total = (size_t)R * Dw * 32;
@@ -1416,7 +1468,9 @@ static int encode_rows_impl(const float* x, int R, int D, int T, const snn_param
     if (wm) {
         if (!encode_rows_wm_ok(x, D)) return fail(-1, "snn_encode_rows: word-major planes need D %% 32 == 0 and 16-byte aligned rows");
         const dim3 g(cdiv(Dw, 8), cdiv(R, 32));
-        if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_rows_wm<ENC_QUANT>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
+        if (fdt == SNN_FEAT_F16) launch_encode_rows_wm_h<feat_f16>(em, g, (hipStream_t)s, x_v, R, D, T, np, *eth, planes, plane_stride);
+        else if (fdt == SNN_FEAT_BF16) launch_encode_rows_wm_h<feat_bf16>(em, g, (hipStream_t)s, x_v, R, D, T, np, *eth, planes, plane_stride);
+        else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_rows_wm<ENC_QUANT>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
         else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_rows_wm<ENC_ZR>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
         else hipLaunchKernelGGL(k_encode_rows_wm<ENC_GENERIC>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
         SNN_CHECK_LAUNCH("k_encode_rows_wm");
@@ -1472,11 +1526,13 @@ int snn_nms_sorted(const float* boxes_sorted, const int* category_sorted, int n,
 
 static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois, const int* roi_batch,
                                  const int* roi_level, int R, int T, const snn_params* p, uint32_t* planes,
-                                 size_t plane_stride, float* pooled_dbg, bool wm, snn_stream_t s, bool periods = false) {
+                                 size_t plane_stride, float* pooled_dbg, bool wm, snn_stream_t s, bool periods = false, int fdt = SNN_FEAT_F32) {
     if (!levels_host || n_levels <= 0 || n_levels > 4 || C <= 0 || !rois || !roi_batch || !roi_level || R <= 0 || !p ||
         !planes)
         return fail(-1, "snn_roi_align_encode: bad argument");
     if (check_T(T, "snn_roi_align_encode")) return -1;
+    for (int l = 0; l < n_levels; ++l)
+        if (check_feat(levels_host[l].feat, fdt, "snn_roi_align_encode")) return -1;
     RoiArgs a;
     memset(&a, 0, sizeof(a));
     for (int l = 0; l < n_levels; ++l) {
@@ -1499,6 +1555,7 @@ static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels,
     bool tab_ok = wm && knobs().roi_tab;
     for (int l = 0; l < n_levels && tab_ok; ++l)
         tab_ok = a.lv[l].W >= 2 && (long long)C * a.lv[l].H * a.lv[l].W < (1ll << 29);
+    if (fdt != SNN_FEAT_F32 && !tab_ok) return SNN_STATUS_NO_TYPED_KERNEL;      // (typed form of the table kernel only; nothing enqueued)
     if (tab_ok) {
         // work-group = 16 RoIs (4 per wave) x 2 groups of 64 elements: small blocks keep the channel window of an XCD narrow (its
         // work-groups sweep the channels in step, snn_encode.h) - 77 % L2 hits against 21 % for 32 RoIs x 7 groups, 0.25 against
@@ -1508,7 +1565,11 @@ static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels,
         while ((size_t)T * 2 * a.E * 16 * a.RW > 49152 && a.E > 1) --a.E;
         a.n_rg = cdiv(R, 4 * a.RW);
         const int n_eblk = cdiv(a.Dw, 2 * a.E);
-        hipLaunchKernelGGL(k_roi_align_encode_tab, dim3(cdiv(n_eblk, 8) * 8 * a.n_rg), dim3(256), (size_t)T * 2 * a.E * 16 * a.RW, (hipStream_t)s, a);
+        const dim3 gt(cdiv(n_eblk, 8) * 8 * a.n_rg);
+        const size_t lds = (size_t)T * 2 * a.E * 16 * a.RW;
+        if (fdt == SNN_FEAT_F16) hipLaunchKernelGGL(k_roi_align_encode_tab_h<feat_f16>, gt, dim3(256), lds, (hipStream_t)s, a);
+        else if (fdt == SNN_FEAT_BF16) hipLaunchKernelGGL(k_roi_align_encode_tab_h<feat_bf16>, gt, dim3(256), lds, (hipStream_t)s, a);
+        else hipLaunchKernelGGL(k_roi_align_encode_tab, gt, dim3(256), lds, (hipStream_t)s, a);
     } else if (wm) hipLaunchKernelGGL(k_roi_align_encode_wm, dim3(cdiv(a.Dw, 2), cdiv(R, 32)), dim3(256), 0, (hipStream_t)s, a);
     else hipLaunchKernelGGL(k_roi_align_encode, dim3(cdiv(a.Dw * 32, 256), R), dim3(256), 0, (hipStream_t)s, a);
     SNN_CHECK_LAUNCH("k_roi_align_encode");
@@ -1518,9 +1579,15 @@ static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels,
 int snn_roi_align_encode(const snn_roi_level* levels_host, int n_levels, int C, const float* rois, const int* roi_batch,
                          const int* roi_level, int R, int T, const snn_params* p, uint32_t* planes,
                          size_t plane_stride, float* pooled_dbg, snn_stream_t s) {
+    return snn_roi_align_encode_typed(levels_host, SNN_FEAT_F32, n_levels, C, rois, roi_batch, roi_level, R, T, p, planes, plane_stride, pooled_dbg, s);
+}
+
+int snn_roi_align_encode_typed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois, const int* roi_batch,
+                               const int* roi_level, int R, int T, const snn_params* p, uint32_t* planes,
+                               size_t plane_stride, float* pooled_dbg, snn_stream_t s) {
     // (SNN_STAGE_PLANES=wm, tests / tools: the planes come back word-major [T][Dw][R] - the layout and the kernels the fused head uses)
     return roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, T, p, planes, plane_stride, pooled_dbg,
-                                 knobs().stage_wm, s, knobs().stage_periods && p && p->v_leak == 0.0f && p->v_reset == 0.0f);
+                                 knobs().stage_wm, s, knobs().stage_periods && p && p->v_leak == 0.0f && p->v_reset == 0.0f, fdt);
 }
 
 // shared by snn_conv3x3_lif (one level) and snn_rpn_head_forward (all levels in one launch)
@@ -1883,7 +1950,8 @@ struct RpnReadouts { const int* steps; int n; };
 static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
                          const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
                          float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
-                         float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, const RpnReadouts* ro, snn_stream_t stream) {
+                         float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, const RpnReadouts* ro, snn_stream_t stream,
+                         int fdt = SNN_FEAT_F32) {
     if (!lv || !p || !w_shared_packed || !w_heads_packed || !out_logits || !out_bbox || !ws)
         return fail(-1, "snn_rpn_head_forward: null argument");
     if (n_levels <= 0 || n_levels > SNN_MAX_LEVELS) return fail(-1, "snn_rpn_head_forward: n_levels=%d", n_levels);
@@ -1897,6 +1965,8 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
     for (int l = 0; l < n_levels; ++l)
         if (!lv[l].feat || lv[l].N <= 0 || lv[l].H <= 0 || lv[l].W <= 0)
             return fail(-1, "snn_rpn_head_forward: bad level %d", l);
+    for (int l = 0; l < n_levels; ++l)
+        if (check_feat(lv[l].feat, fdt, "snn_rpn_head_forward")) return -1;
     int max_n = 0;
     const long long P = rpn_positions(lv, n_levels, &max_n);
     size_t o_spk, o_cur, o_cnt, need;
@@ -1960,7 +2030,9 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         const EncTh* eth;
         const int em = enc_mode(np, &eth);
         const dim3 ge(blocks, cdiv(Cw, ENC_WB));
-        if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_levels<ENC_QUANT>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, enc_cmp, 2);
+        if (fdt == SNN_FEAT_F16) launch_encode_levels_h<feat_f16>(em, ge, Tc, s, el, C, Cw, np, *eth, enc, enc_stride, wm_rows, enc_cmp);
+        else if (fdt == SNN_FEAT_BF16) launch_encode_levels_h<feat_bf16>(em, ge, Tc, s, el, C, Cw, np, *eth, enc, enc_stride, wm_rows, enc_cmp);
+        else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_levels<ENC_QUANT>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, enc_cmp, 2);
         else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_levels<ENC_ZR>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
         else hipLaunchKernelGGL(k_encode_levels<ENC_GENERIC>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
         SNN_CHECK_LAUNCH("k_encode_levels");
@@ -2020,27 +2092,43 @@ int snn_rpn_head_forward_stages(const snn_rpn_level* lv, int n_levels, int C, in
                                 const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
                                 float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
                                 float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, snn_stream_t stream) {
+    return snn_rpn_head_forward_stages_typed(lv, SNN_FEAT_F32, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox,
+                                             spike_counts, sum_logits, sum_bbox, ws, ws_bytes, stage_mask, stream);
+}
+
+int snn_rpn_head_forward_stages_typed(const snn_rpn_level* lv, int fdt, int n_levels, int C, int A, int T, const snn_params* p,
+                                      const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                                      float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                      float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, snn_stream_t stream) {
     return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
-                         sum_bbox, ws, ws_bytes, stage_mask, nullptr, stream);
+                         sum_bbox, ws, ws_bytes, stage_mask, nullptr, stream, fdt);
 }
 
 int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
                          const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
                          float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
                          void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
-                         sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, nullptr, stream);
+    return snn_rpn_head_forward_stages_typed(lv, SNN_FEAT_F32, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox,
+                                             spike_counts, sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, stream);
 }
 
 int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,
                                   const snn_params* p, const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
                                   float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
                                   void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return snn_rpn_head_forward_readouts_typed(lv, SNN_FEAT_F32, n_levels, C, A, steps, n_steps, p, w_shared_packed, w_heads_packed, out_logits,
+                                               out_bbox, spike_counts, sum_logits, sum_bbox, ws, ws_bytes, stream);
+}
+
+int snn_rpn_head_forward_readouts_typed(const snn_rpn_level* lv, int fdt, int n_levels, int C, int A, const int* steps, int n_steps,
+                                        const snn_params* p, const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
+                                        float* out_bbox, unsigned long long* spike_counts, float* sum_logits, float* sum_bbox,
+                                        void* ws, size_t ws_bytes, snn_stream_t stream) {
     if (check_steps(steps, n_steps, "snn_rpn_head_forward_readouts")) return -1;
     if ((sum_logits == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_rpn_head_forward_readouts: sum_logits and sum_bbox go together");
     const RpnReadouts ro{steps, n_steps};
     return rpn_head_impl(lv, n_levels, C, A, steps[n_steps - 1], p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts,
-                         sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, &ro, stream);
+                         sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, &ro, stream, fdt);
 }
 
 // ---- finished spike-rate tensors -------------------------------------------------------------------
@@ -2464,7 +2552,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
                           stream);                                                                       // :505-510
 }
 
-static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                                  float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream, const DetReadouts* ro) {
@@ -2472,6 +2560,7 @@ static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, in
         return fail(-1, "snn_det_head_forward: null argument");
     if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward: bad shape");
     if (check_T(T, "snn_det_head_forward")) return -1;          // (the row-fed entry points check T before the workspace)
+    if (check_feat(x, fdt, "snn_det_head_forward")) return -1;
     DetPlan dp;
     int rc;
     if ((rc = det_plan("snn_det_head_forward", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, encode_rows_wm_ok(x, D), ws_bytes, &dp)))
@@ -2487,8 +2576,9 @@ static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, in
         // eight waves per block where only two blocks fit a CU's LDS (T_det = 12: -2 us, T_det = 24: -10 us), four where three fit (T_det = 16: eight
         // were 9 us slower) - profiles/r5_encoder_nw_ab.txt
         const int nw = knobs().encp_nw ? (knobs().encp_nw == 4 ? 4 : 8) : (lds > 53 * 1024 ? 8 : 4);
-        const void* kern = rb == 16 ? (nw == 8 ? (const void*)k_encode_rows_perm<49, 16, 8> : (const void*)k_encode_rows_perm<49, 16, 4>)
-                                    : (nw == 8 ? (const void*)k_encode_rows_perm<49, 8, 8> : (const void*)k_encode_rows_perm<49, 8, 4>);
+        const void* kern = fdt == SNN_FEAT_F16 ? encode_rows_perm_h_kernel<feat_f16>(rb, nw) : fdt == SNN_FEAT_BF16 ? encode_rows_perm_h_kernel<feat_bf16>(rb, nw)
+                           : rb == 16 ? (nw == 8 ? (const void*)k_encode_rows_perm<49, 16, 8> : (const void*)k_encode_rows_perm<49, 16, 4>)
+                                      : (nw == 8 ? (const void*)k_encode_rows_perm<49, 8, 8> : (const void*)k_encode_rows_perm<49, 8, 4>);
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         uint32_t* planes_f = (uint32_t*)((char*)ws + dp.o_enc);
@@ -2499,14 +2589,14 @@ static int det_head_forward_impl(const float* x, int R, int D, int Hd, int K, in
         if (e != hipSuccess) return fail(-3, "k_encode_rows_perm launch failed: %s", hipGetErrorString(e));
         SNN_CHECK_LAUNCH("k_encode_rows_perm");
     } else if ((rc = encode_rows_impl(x, R, D, dp.win.enc_steps, p, (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), dp.wm, stream,
-                                      dp.per))) {
-        return rc;
+                                      dp.per, fdt))) {
+        return rc;                                              // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
     }
     return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
 }
 
-static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
+static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
                                           const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
                                           const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
                                           const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
@@ -2546,11 +2636,16 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
         fa.RW = RW; fa.n_rg = cdiv(R, 4 * RW);
         const int n_cp = C / 64, n_items = fa.n_rg * 7;
         const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
-        hipLaunchKernelGGL(k_roi_align_encode_perm<RW>, dim3(grid), dim3(256), (size_t)fa.T * (7 + 8) * 4 * RW * 8, (hipStream_t)stream, fa);     // word pairs + raw ballots
+        const size_t lds = (size_t)fa.T * (7 + 8) * 4 * RW * 8;                  // word pairs + raw ballots
+        for (int l = 0; l < n_levels; ++l)
+            if (check_feat(levels_host[l].feat, fdt, "snn_det_head_forward_roialign")) return -1;
+        if (fdt == SNN_FEAT_F16) hipLaunchKernelGGL((k_roi_align_encode_perm_h<RW, feat_f16>), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
+        else if (fdt == SNN_FEAT_BF16) hipLaunchKernelGGL((k_roi_align_encode_perm_h<RW, feat_bf16>), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
+        else hipLaunchKernelGGL(k_roi_align_encode_perm<RW>, dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
         SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
     } else if ((rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, dp.win.enc_steps, p,
-                                           (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per))) {
-        return rc;
+                                           (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per, fdt))) {
+        return rc;                                              // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
     }
     return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
@@ -2560,15 +2655,23 @@ int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, in
                          const void* w6_packed, const void* w7_packed, const float* w_heads_packed,
                          float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                          float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, 0, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count,
-                                 sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+    return snn_det_head_forward_k_typed(x, SNN_FEAT_F32, R, D, Hd, K, K4, T, p, w6_packed, 0, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+                                        spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
 }
 
 int snn_det_head_forward_k(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
                            const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                            float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                            float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return det_head_forward_impl(x, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+    return snn_det_head_forward_k_typed(x, SNN_FEAT_F32, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
+                                        spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
+}
+
+int snn_det_head_forward_k_typed(const void* x, int fdt, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
                                  spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
 }
 
@@ -2578,9 +2681,17 @@ int snn_det_head_forward_readouts(const float* x, int R, int D, int Hd, int K, i
                                   const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                                   float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                                   float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return snn_det_head_forward_readouts_typed(x, SNN_FEAT_F32, R, D, Hd, K, K4, steps, n_steps, p, w6_packed, w6_inner, w7_packed, w_heads_packed,
+                                               out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
+}
+
+int snn_det_head_forward_readouts_typed(const void* x, int fdt, int R, int D, int Hd, int K, int K4, const int* steps, int n_steps,
+                                        const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                        const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                        uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
     DetReadouts ro;
     if (det_readouts("snn_det_head_forward_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
-    return det_head_forward_impl(x, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
+    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
                                  spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, &ro);
 }
 
@@ -2590,9 +2701,9 @@ int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels
                                   const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                   uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                   snn_stream_t stream) {
-    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, 0,
-                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
-                                          ws_bytes, stream, nullptr);
+    return snn_det_head_forward_roialign_k_typed(levels_host, SNN_FEAT_F32, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, 0,
+                                                 w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
+                                                 ws_bytes, stream);
 }
 
 int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
@@ -2601,7 +2712,18 @@ int snn_det_head_forward_roialign_k(const snn_roi_level* levels_host, int n_leve
                                     const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                     uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                     snn_stream_t stream) {
-    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
+    return snn_det_head_forward_roialign_k_typed(levels_host, SNN_FEAT_F32, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed,
+                                                 w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox,
+                                                 ws, ws_bytes, stream);
+}
+
+int snn_det_head_forward_roialign_k_typed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
+                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                          snn_stream_t stream) {
+    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
                                           w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
                                           ws_bytes, stream, nullptr);
 }
@@ -2612,9 +2734,20 @@ int snn_det_head_forward_roialign_readouts(const snn_roi_level* levels_host, int
                                            const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                            uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                            snn_stream_t stream) {
+    return snn_det_head_forward_roialign_readouts_typed(levels_host, SNN_FEAT_F32, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps,
+                                                        n_steps, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+                                                        spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream);
+}
+
+int snn_det_head_forward_roialign_readouts_typed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
+                                                 const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, const int* steps,
+                                                 int n_steps, const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                                 const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                                 uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                                 snn_stream_t stream) {
     DetReadouts ro;
     if (det_readouts("snn_det_head_forward_roialign_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
-    return det_head_forward_roialign_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
+    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
                                           w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
                                           ws_bytes, stream, &ro);
 }

@@ -59,6 +59,46 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
+# Half-precision features (include/snn_hip.h, SNN_FEAT_*): fp16 / bf16 CUDA tensors go to the typed entry points uncast - an element means its
+# exact fp32 value, the encoder kernels widen it in registers, outputs stay fp32.  Every other dtype is widened to fp32 as before.
+_HALF = {torch.float16: _lib.FEAT_DTYPES["f16"], torch.bfloat16: _lib.FEAT_DTYPES["bf16"]}
+# call record of the typed path: "f16" / "bf16" = typed calls that ran, "no_typed_kernel" = calls whose launch plan has no typed encoder
+# (the typed entry enqueued nothing; the features were widened and the fp32 entry ran)
+feature_calls = {"f16": 0, "bf16": 0, "no_typed_kernel": 0}
+
+
+def _feat(t: torch.Tensor) -> torch.Tensor:
+    """a feature tensor as the kernels take it: half-precision CUDA tensors contiguous and 16-byte aligned, else fp32 contiguous"""
+    if t.is_cuda and t.dtype in _HALF:
+        t = t.detach().contiguous()
+        return t.clone() if t.data_ptr() % 16 else t
+    return _f32c(t)
+
+
+def _feat_levels(feats, what: str):
+    """-> (the levels as the kernels take them, their common SNN_FEAT_* code); levels of one call share a dtype"""
+    feats = list(feats)
+    for f in feats:
+        _need_gpu(f, what)
+    if any(f.dtype in _HALF for f in feats) and len({f.dtype for f in feats}) > 1:
+        raise _lib.SnnHipError("%s: the levels of one call must share a dtype, got %s" % (what, sorted({str(f.dtype) for f in feats})))
+    feats = [_feat(f) for f in feats]
+    return feats, (_HALF.get(feats[0].dtype, 0) if feats else 0)
+
+
+def _typed_call(call, feats, fdt: int, what: str) -> None:
+    """call(feats, fdt) -> status.  Half features whose launch plan has no typed encoder kernel (SNN_STATUS_NO_TYPED_KERNEL: nothing was
+    enqueued) are widened and go through the fp32 entry, as every feature did before"""
+    rc = call(feats, fdt)
+    if fdt and rc == _lib.NO_TYPED_KERNEL:
+        feature_calls["no_typed_kernel"] += 1
+        feats, fdt = [_f32c(f) for f in feats], 0
+        rc = call(feats, fdt)
+    _lib.check(rc, what)
+    if fdt:
+        feature_calls["f16" if fdt == 1 else "bf16"] += 1
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -392,15 +432,18 @@ def affine_act_nchw(x: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, re
 
 
 def encode_nchw(feat: torch.Tensor, T: int, p: snn_params) -> torch.Tensor:
-    """[N,C,H,W] fp32 -> spike bit-planes uint32 viewed as int32 [T, N*H*W, Cw]"""
-    _need_gpu(feat, "feature map")
+    """[N,C,H,W] fp32 (or fp16 / bf16, uncast) -> spike bit-planes uint32 viewed as int32 [T, N*H*W, Cw]"""
     lib = _lib.load()
-    feat = _f32c(feat)
+    (feat,), fdt = _feat_levels([feat], "feature map")
     N, Cc, H, W = feat.shape
     Cw = cdiv(Cc, 32)
     planes = torch.empty((T, N * H * W, Cw), dtype=torch.int32, device=feat.device)
-    _lib.check(lib.snn_encode_nchw(_ptr(feat), N, Cc, H, W, T, C.byref(p), _ptr(planes), N * H * W * Cw, _stream()),
-               "snn_encode_nchw")
+    if not fdt:
+        _lib.check(lib.snn_encode_nchw(_ptr(feat), N, Cc, H, W, T, C.byref(p), _ptr(planes), N * H * W * Cw, _stream()),
+                   "snn_encode_nchw")
+        return planes
+    _typed_call(lambda fs, d: lib.snn_encode_nchw_typed(_ptr(fs[0]), d, N, Cc, H, W, T, C.byref(p), _ptr(planes), N * H * W * Cw, _stream()),
+                [feat], fdt, "snn_encode_nchw")
     return planes
 
 
@@ -512,18 +555,21 @@ _WS = _Workspace()
 _WS_RATES = _Workspace()                     # partial sums of snn_rpn_rates (must not alias the heads' workspace)
 
 
+def _rpn_table(feats):
+    return (snn_rpn_level * len(feats))(*[snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0) for f in feats])
+
+
 def _rpn_levels(feats: Sequence[torch.Tensor], C_: int):
-    """checked fp32 feature maps [N, C_, H, W] -> (the maps, their snn_rpn_level table, output rows per level, largest N)"""
+    """checked feature maps [N, C_, H, W] (fp32, or fp16 / bf16 uncast) -> (the maps, their SNN_FEAT_* code, their snn_rpn_level table,
+    output rows per level, largest N)"""
     if len(feats) == 0 or len(feats) > _lib.SNN_MAX_LEVELS:
         raise _lib.SnnHipError("RPN head takes 1..%d feature levels, got %d" % (_lib.SNN_MAX_LEVELS, len(feats)))
-    feats = [_f32c(f) for f in feats]
+    feats, fdt = _feat_levels(feats, "feature map")
     for f in feats:
-        _need_gpu(f, "feature map")
         if f.dim() != 4 or f.shape[1] != C_:
             raise _lib.SnnHipError("feature map must be [N,%d,H,W], got %s" % (C_, tuple(f.shape)))
-    lv = (snn_rpn_level * len(feats))(*[snn_rpn_level(f.data_ptr(), f.shape[0], f.shape[2], f.shape[3], 0) for f in feats])
     rows = [f.shape[0] * f.shape[2] * f.shape[3] for f in feats]
-    return feats, lv, rows, max(f.shape[0] for f in feats)
+    return feats, fdt, _rpn_table(feats), rows, max(f.shape[0] for f in feats)
 
 
 def _rpn_outputs(P: int, A: int, n_levels: int, max_n: int, spike_rates: bool, dev, n=None):
@@ -554,15 +600,16 @@ def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: 
     """Returns (out_logits [P,A], out_bbox [P,4A], level_rows, extras) — position-major outputs.
     ``stage_mask`` (SNN_STAGE_*: 1 encode, 2 conv+LIF, 4 LI heads) is for profiling only."""
     lib = _lib.load()
-    feats, lv, rows, max_n = _rpn_levels(feats, C_)
+    feats, fdt, lv, rows, max_n = _rpn_levels(feats, C_)
     dev = feats[0].device
     ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, T, p.precision))
     out_logits, out_bbox, (counts, sum_l, sum_b) = _rpn_outputs(sum(rows), A, len(feats), max_n, spike_rates, dev)
-    _lib.check(lib.snn_rpn_head_forward_stages(lv, len(feats), C_, A, T, C.byref(p), _ptr(w_shared_packed),
-                                               _ptr(w_heads_packed), _ptr(out_logits), _ptr(out_bbox),
-                                               _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(),
-                                               int(stage_mask), _stream()),
-               "snn_rpn_head_forward")
+    tail = (C_, A, T, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed), _ptr(out_logits), _ptr(out_bbox),
+            _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(), int(stage_mask), _stream())
+    if not fdt:
+        _lib.check(lib.snn_rpn_head_forward_stages(lv, len(feats), *tail), "snn_rpn_head_forward")
+    else:
+        _typed_call(lambda fs, d: lib.snn_rpn_head_forward_stages_typed(_rpn_table(fs), d, len(fs), *tail), feats, fdt, "snn_rpn_head_forward")
     rates = None
     if spike_rates and stage_mask == 7:
         rates = _rpn_rates(lib, lv, len(feats), C_, A, T, max_n, counts, sum_l, sum_b, dev)
@@ -570,9 +617,9 @@ def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: 
 
 
 def _det_rows(x: torch.Tensor) -> torch.Tensor:
-    """box features -> fp32 rows [R, D] (a view at an odd offset is copied: the word-major encoder loads 16-byte pieces)"""
+    """box features -> rows [R, D], fp32 or fp16 / bf16 uncast (a view at an odd offset is copied: the word-major encoder loads 16-byte pieces)"""
     _need_gpu(x, "box features")
-    x = _f32c(x).flatten(1)
+    x = _feat(x).flatten(1)
     return x.clone() if x.data_ptr() % 16 else x
 
 
@@ -601,10 +648,12 @@ def det_head_forward(x: torch.Tensor, Hd: int, K: int, K4: int, T: int, p: snn_p
     out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, x.device)
     if R:
         ws = _det_ws(lib, x.device, R, D, Hd, K, K4, T, p)
-        _lib.check(lib.snn_det_head_forward_k(_ptr(x), R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                              _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
-                                              _ptr(ws), ws.numel(), _stream()),
-                   "snn_det_head_forward")
+        tail = (R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls),
+                _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
+        if x.dtype not in _HALF:
+            _lib.check(lib.snn_det_head_forward_k(_ptr(x), *tail), "snn_det_head_forward")
+        else:
+            _typed_call(lambda xs, d: lib.snn_det_head_forward_k_typed(_ptr(xs[0]), d, *tail), [x], _HALF[x.dtype], "snn_det_head_forward")
     return out_cls, out_bbox, extras
 
 
@@ -624,14 +673,14 @@ def det_rates(extras, D: int, Hd: int, K: int, K4: int, T: int, only_one_bbox: b
 # RoIAlign fused with the detector encoder
 # ---------------------------------------------------------------------------------------------
 def _roi_feed(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor, roi_level: torch.Tensor):
-    """the RoIAlign feed: (snn_roi_level table, the fp32 maps it points to, channels, rois [R, 4] fp32, roi_batch, roi_level int32)"""
-    keep, lvs = [], []
-    for f, sc in zip(feats, scales):
-        _need_gpu(f, "feature map")
-        keep.append(_f32c(f))
-        lvs.append(snn_roi_level(keep[-1].data_ptr(), f.shape[2], f.shape[3], float(sc), 0))
-    lv = (snn_roi_level * len(lvs))(*lvs)
-    return (lv, keep, keep[0].shape[1], _f32c(rois), roi_batch.to(torch.int32).contiguous(),
+    """the RoIAlign feed: (maker of the snn_roi_level table of a list of maps, the maps (fp32, or fp16 / bf16 uncast), their SNN_FEAT_* code,
+    channels, rois [R, 4] fp32, roi_batch, roi_level int32)"""
+    scales = [float(sc) for sc in scales]
+    keep, fdt = _feat_levels(list(feats)[:len(scales)], "feature map")
+
+    def table(maps):
+        return (snn_roi_level * len(maps))(*[snn_roi_level(f.data_ptr(), f.shape[2], f.shape[3], sc, 0) for f, sc in zip(maps, scales)])
+    return (table, keep, fdt, keep[0].shape[1], _f32c(rois), roi_batch.to(torch.int32).contiguous(),
             roi_level.to(torch.int32).contiguous())
 
 
@@ -640,28 +689,34 @@ def roi_align_encode(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor,
     """feats: list of [N,C,H,W]; rois [R,4]; roi_batch/roi_level int32 [R] -> encoder planes int32 [T, R, Dw]
     (+ the pooled [R, C*49] features when asked: parity tests)"""
     lib = _lib.load()
-    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
+    table, keep, fdt, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
     Dw = cdiv(Cc * 49, 32)
     planes = torch.empty((T, R, Dw), dtype=torch.int32, device=rois.device)
     pooled = torch.empty((R, Cc * 49), dtype=torch.float32, device=rois.device) if want_pooled else None
-    _lib.check(lib.snn_roi_align_encode(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, T, C.byref(p),
-                                        _ptr(planes), R * Dw, _ptr(pooled), _stream()), "snn_roi_align_encode")
+    tail = (Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, T, C.byref(p), _ptr(planes), R * Dw, _ptr(pooled), _stream())
+    if not fdt:
+        _lib.check(lib.snn_roi_align_encode(table(keep), len(keep), *tail), "snn_roi_align_encode")
+    else:
+        _typed_call(lambda fs, d: lib.snn_roi_align_encode_typed(table(fs), d, len(fs), *tail), keep, fdt, "snn_roi_align_encode")
     return (planes, pooled) if want_pooled else planes
 
 
 def det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, Hd: int, K: int, K4: int, T: int, p: snn_params,
                               w6_packed, w7_packed, w_heads_packed, spike_rates: bool = False, w6_inner: int = 0):
     lib = _lib.load()
-    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
+    table, keep, fdt, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
     out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, rois.device)
     if R:
         ws = _det_ws(lib, rois.device, R, Cc * 49, Hd, K, K4, T, p)
-        _lib.check(lib.snn_det_head_forward_roialign_k(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K,
-                                                       K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                                       _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
-                                                       _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_roialign")
+        tail = (Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner),
+                _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
+        if not fdt:
+            _lib.check(lib.snn_det_head_forward_roialign_k(table(keep), len(keep), *tail), "snn_det_head_forward_roialign")
+        else:
+            _typed_call(lambda fs, d: lib.snn_det_head_forward_roialign_k_typed(table(fs), d, len(fs), *tail), keep, fdt,
+                        "snn_det_head_forward_roialign")
     return out_cls, out_bbox, extras
 
 
@@ -715,14 +770,18 @@ def rpn_head_forward_readouts(feats: Sequence[torch.Tensor], C_: int, A: int, st
     (counts [n,levels,max_n], sum_l, sum_b, rates: list of [levels,3,max_n,2] per readout))"""
     steps = check_steps(steps)
     lib = _lib.load()
-    feats, lv, rows, max_n = _rpn_levels(feats, C_)
+    feats, fdt, lv, rows, max_n = _rpn_levels(feats, C_)
     dev = feats[0].device
     ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, steps[-1], p.precision))
     out_l, out_b, (counts, sum_l, sum_b) = _rpn_outputs(sum(rows), A, len(feats), max_n, spike_rates, dev, n=len(steps))
     st, ns = _steps_arg(steps)
-    _lib.check(lib.snn_rpn_head_forward_readouts(lv, len(feats), C_, A, st, ns, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed),
-                                                 _ptr(out_l), _ptr(out_b), _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(),
-                                                 _stream()), "snn_rpn_head_forward_readouts")
+    tail = (C_, A, st, ns, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed), _ptr(out_l), _ptr(out_b), _ptr(counts), _ptr(sum_l),
+            _ptr(sum_b), _ptr(ws), ws.numel(), _stream())
+    if not fdt:
+        _lib.check(lib.snn_rpn_head_forward_readouts(lv, len(feats), *tail), "snn_rpn_head_forward_readouts")
+    else:
+        _typed_call(lambda fs, d: lib.snn_rpn_head_forward_readouts_typed(_rpn_table(fs), d, len(fs), *tail), feats, fdt,
+                    "snn_rpn_head_forward_readouts")
     rates = None
     if spike_rates:
         rates = [_rpn_rates(lib, lv, len(feats), C_, A, T, max_n, counts[j], sum_l[j], sum_b[j], dev) for j, T in enumerate(steps)]
@@ -740,9 +799,13 @@ def det_head_forward_readouts(x: torch.Tensor, Hd: int, K: int, K4: int, steps, 
     if R:
         ws = _det_ws(lib, x.device, R, D, Hd, K, K4, steps[-1], p)
         st, ns = _steps_arg(steps)
-        _lib.check(lib.snn_det_head_forward_readouts(_ptr(x), R, D, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner),
-                                                     _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
-                                                     _ptr(ws), ws.numel(), _stream()), "snn_det_head_forward_readouts")
+        tail = (R, D, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls),
+                _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
+        if x.dtype not in _HALF:
+            _lib.check(lib.snn_det_head_forward_readouts(_ptr(x), *tail), "snn_det_head_forward_readouts")
+        else:
+            _typed_call(lambda xs, d: lib.snn_det_head_forward_readouts_typed(_ptr(xs[0]), d, *tail), [x], _HALF[x.dtype],
+                        "snn_det_head_forward_readouts")
     return out_cls, out_bbox, extras
 
 
@@ -751,17 +814,19 @@ def det_head_forward_roialign_readouts(feats, scales, rois, roi_batch, roi_level
     """det_head_forward_readouts fed straight from the FPN maps (RoIAlign fused with the encoder)"""
     steps = check_steps(steps)
     lib = _lib.load()
-    lv, keep, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
+    table, keep, fdt, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
     out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, rois.device, n=len(steps))
     if R:
         ws = _det_ws(lib, rois.device, R, Cc * 49, Hd, K, K4, steps[-1], p)
         st, ns = _steps_arg(steps)
-        _lib.check(lib.snn_det_head_forward_roialign_readouts(lv, len(keep), Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4,
-                                                              st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed),
-                                                              _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras),
-                                                              _ptr(ws), ws.numel(), _stream()),
-                   "snn_det_head_forward_roialign_readouts")
+        tail = (Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4, st, ns, C.byref(p), _ptr(w6_packed), int(w6_inner),
+                _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
+        if not fdt:
+            _lib.check(lib.snn_det_head_forward_roialign_readouts(table(keep), len(keep), *tail), "snn_det_head_forward_roialign_readouts")
+        else:
+            _typed_call(lambda fs, d: lib.snn_det_head_forward_roialign_readouts_typed(table(fs), d, len(fs), *tail), keep, fdt,
+                        "snn_det_head_forward_roialign_readouts")
     return out_cls, out_bbox, extras
 
 # ---------------------------------------------------------------------------------------------
