@@ -509,37 +509,39 @@ __global__ __launch_bounds__(1024) void k_det_payload(const float* __restrict__ 
     if (tid == 0) counts[img] = n;
 }
 
-// ---- launches of the typed (half-precision feature) encoders: the arguments of the fp32 launch next to which each is called, per encoder mode
-template <typename FT>
-static void launch_encode_nchw_h(int em, dim3 g, int T, hipStream_t s, const void* feat, int C, int HW, int Cw, const NeuronP& np, const EncTh& eth,
-                                 uint32_t* planes, size_t plane_stride) {
-    const FT* f = (const FT*)feat;
-    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_nchw_h<ENC_QUANT, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
-    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_nchw_h<ENC_ZR, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
-    else hipLaunchKernelGGL((k_encode_nchw_h<ENC_GENERIC, FT>), g, dim3(256), ENC_LDS_BYTES(T), s, f, C, HW, Cw, T, np, eth, planes, plane_stride);
+// ---- the encoder kernel of a launch: K<..> for fp32 features, K_h<.., feat_f16 | feat_bf16> for half-precision ones (fdt has passed check_feat)
+#define ENC_PICKER(fn, K)                                                                                                                                  \
+    template <int EM>                                                                                                                                      \
+    static const void* fn##_of(int fdt) {                                                                                                                  \
+        return fdt == SNN_FEAT_F16 ? (const void*)K##_h<EM, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)K##_h<EM, feat_bf16> : (const void*)K<EM>;      \
+    }                                                                                                                                                      \
+    static const void* fn(int em, int fdt) { return em == ENC_QUANT ? fn##_of<ENC_QUANT>(fdt) : em == ENC_ZR ? fn##_of<ENC_ZR>(fdt) : fn##_of<ENC_GENERIC>(fdt); }
+ENC_PICKER(encode_nchw_kernel, k_encode_nchw)
+ENC_PICKER(encode_levels_kernel, k_encode_levels)
+ENC_PICKER(encode_rows_wm_kernel, k_encode_rows_wm)
+#undef ENC_PICKER
+template <int RB, int NW>
+static const void* encode_rows_perm_of(int fdt) {
+    return fdt == SNN_FEAT_F16 ? (const void*)k_encode_rows_perm_h<49, RB, NW, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)k_encode_rows_perm_h<49, RB, NW, feat_bf16>
+                                                                                                                 : (const void*)k_encode_rows_perm<49, RB, NW>;
 }
-
-template <typename FT>
-static void launch_encode_rows_wm_h(int em, dim3 g, hipStream_t s, const void* x, int R, int D, int T, const NeuronP& np, const EncTh& eth,
-                                    uint32_t* planes, size_t plane_stride) {
-    const FT* xf = (const FT*)x;
-    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_QUANT, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
-    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_ZR, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
-    else hipLaunchKernelGGL((k_encode_rows_wm_h<ENC_GENERIC, FT>), g, dim3(256), 0, s, xf, R, D, T, np, eth, planes, plane_stride);
+static const void* encode_rows_perm_kernel(int rb, int nw, int fdt) {
+    return rb == 16 ? (nw == 8 ? encode_rows_perm_of<16, 8>(fdt) : encode_rows_perm_of<16, 4>(fdt)) : (nw == 8 ? encode_rows_perm_of<8, 8>(fdt) : encode_rows_perm_of<8, 4>(fdt));
 }
-
-template <typename FT>                               // the typed forms of rpn_head_impl's encoder launch (same arguments per encoder mode)
-static void launch_encode_levels_h(int em, dim3 ge, int Tc, hipStream_t s, const EncLevels& el, int C, int Cw, const NeuronP& np, const EncTh& eth,
-                                   uint32_t* enc, size_t enc_stride, size_t wm_rows, uint32_t* enc_cmp) {
-    if (em == ENC_QUANT) hipLaunchKernelGGL((k_encode_levels_h<ENC_QUANT, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, enc_cmp, 2);
-    else if (em == ENC_ZR) hipLaunchKernelGGL((k_encode_levels_h<ENC_ZR, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
-    else hipLaunchKernelGGL((k_encode_levels_h<ENC_GENERIC, FT>), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
+static const void* roi_align_encode_tab_kernel(int fdt) {
+    return fdt == SNN_FEAT_F16 ? (const void*)k_roi_align_encode_tab_h<feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)k_roi_align_encode_tab_h<feat_bf16>
+                                                                                                         : (const void*)k_roi_align_encode_tab;
 }
-
-template <typename FT>
-static const void* encode_rows_perm_h_kernel(int rb, int nw) {
-    return rb == 16 ? (nw == 8 ? (const void*)k_encode_rows_perm_h<49, 16, 8, FT> : (const void*)k_encode_rows_perm_h<49, 16, 4, FT>)
-                    : (nw == 8 ? (const void*)k_encode_rows_perm_h<49, 8, 8, FT> : (const void*)k_encode_rows_perm_h<49, 8, 4, FT>);
+template <int RW>
+static const void* roi_align_encode_perm_kernel(int fdt) {
+    return fdt == SNN_FEAT_F16 ? (const void*)k_roi_align_encode_perm_h<RW, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)k_roi_align_encode_perm_h<RW, feat_bf16>
+                                                                                                              : (const void*)k_roi_align_encode_perm<RW>;
+}
+// launch of a picked kernel: every argument has exactly its parameter's type (a refused launch is the thread's last error: SNN_CHECK_LAUNCH)
+template <typename... A>
+static void launch_picked(const void* kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... a) {
+    void* kargs[] = {(void*)&a...};
+    (void)hipLaunchKernel(kern, grid, block, kargs, lds, s);
 }
 
 extern "C" {
@@ -1422,11 +1424,7 @@ int snn_encode_nchw_typed(const void* feat_v, int fdt, int N, int C, int H, int 
     const EncTh* eth;
     const int em = enc_mode(np, &eth);
     const dim3 g(cdiv(HW, ENC_PB), cdiv(Cw, ENC_WB), N);
-    if (fdt == SNN_FEAT_F16) launch_encode_nchw_h<feat_f16>(em, g, T, (hipStream_t)s, feat_v, C, HW, Cw, np, *eth, planes, plane_stride);
-    else if (fdt == SNN_FEAT_BF16) launch_encode_nchw_h<feat_bf16>(em, g, T, (hipStream_t)s, feat_v, C, HW, Cw, np, *eth, planes, plane_stride);
-    else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_nchw<ENC_QUANT>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
-    else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_nchw<ENC_ZR>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
-    else hipLaunchKernelGGL(k_encode_nchw<ENC_GENERIC>, g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
+    launch_picked(encode_nchw_kernel(em, fdt), g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
     SNN_CHECK_LAUNCH("k_encode_nchw");
     return 0;
 }
@@ -1468,11 +1466,7 @@ static int encode_rows_impl(const void* x_v, int R, int D, int T, const snn_para
     if (wm) {
         if (!encode_rows_wm_ok(x, D)) return fail(-1, "snn_encode_rows: word-major planes need D %% 32 == 0 and 16-byte aligned rows");
         const dim3 g(cdiv(Dw, 8), cdiv(R, 32));
-        if (fdt == SNN_FEAT_F16) launch_encode_rows_wm_h<feat_f16>(em, g, (hipStream_t)s, x_v, R, D, T, np, *eth, planes, plane_stride);
-        else if (fdt == SNN_FEAT_BF16) launch_encode_rows_wm_h<feat_bf16>(em, g, (hipStream_t)s, x_v, R, D, T, np, *eth, planes, plane_stride);
-        else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_rows_wm<ENC_QUANT>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
-        else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_rows_wm<ENC_ZR>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
-        else hipLaunchKernelGGL(k_encode_rows_wm<ENC_GENERIC>, g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
+        launch_picked(encode_rows_wm_kernel(em, fdt), g, dim3(256), 0, (hipStream_t)s, x, R, D, T, np, *eth, planes, plane_stride);
         SNN_CHECK_LAUNCH("k_encode_rows_wm");
         return 0;
     }
@@ -1567,9 +1561,7 @@ static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels,
         const int n_eblk = cdiv(a.Dw, 2 * a.E);
         const dim3 gt(cdiv(n_eblk, 8) * 8 * a.n_rg);
         const size_t lds = (size_t)T * 2 * a.E * 16 * a.RW;
-        if (fdt == SNN_FEAT_F16) hipLaunchKernelGGL(k_roi_align_encode_tab_h<feat_f16>, gt, dim3(256), lds, (hipStream_t)s, a);
-        else if (fdt == SNN_FEAT_BF16) hipLaunchKernelGGL(k_roi_align_encode_tab_h<feat_bf16>, gt, dim3(256), lds, (hipStream_t)s, a);
-        else hipLaunchKernelGGL(k_roi_align_encode_tab, gt, dim3(256), lds, (hipStream_t)s, a);
+        launch_picked(roi_align_encode_tab_kernel(fdt), gt, dim3(256), lds, (hipStream_t)s, a);
     } else if (wm) hipLaunchKernelGGL(k_roi_align_encode_wm, dim3(cdiv(a.Dw, 2), cdiv(R, 32)), dim3(256), 0, (hipStream_t)s, a);
     else hipLaunchKernelGGL(k_roi_align_encode, dim3(cdiv(a.Dw * 32, 256), R), dim3(256), 0, (hipStream_t)s, a);
     SNN_CHECK_LAUNCH("k_roi_align_encode");
@@ -2030,11 +2022,8 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         const EncTh* eth;
         const int em = enc_mode(np, &eth);
         const dim3 ge(blocks, cdiv(Cw, ENC_WB));
-        if (fdt == SNN_FEAT_F16) launch_encode_levels_h<feat_f16>(em, ge, Tc, s, el, C, Cw, np, *eth, enc, enc_stride, wm_rows, enc_cmp);
-        else if (fdt == SNN_FEAT_BF16) launch_encode_levels_h<feat_bf16>(em, ge, Tc, s, el, C, Cw, np, *eth, enc, enc_stride, wm_rows, enc_cmp);
-        else if (em == ENC_QUANT) hipLaunchKernelGGL(k_encode_levels<ENC_QUANT>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, enc_cmp, 2);
-        else if (em == ENC_ZR) hipLaunchKernelGGL(k_encode_levels<ENC_ZR>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
-        else hipLaunchKernelGGL(k_encode_levels<ENC_GENERIC>, ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, (uint32_t*)nullptr, 0);
+        uint32_t* const cmp_e = em == ENC_QUANT ? enc_cmp : nullptr;         // (the compressed-plane fold: period planes by thresholds only)
+        launch_picked(encode_levels_kernel(em, fdt), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, cmp_e, em == ENC_QUANT ? 2 : 0);
         SNN_CHECK_LAUNCH("k_encode_levels");
     }
     if (stage_mask & SNN_STAGE_CONV_LIF) {
@@ -2576,9 +2565,7 @@ static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, i
         // eight waves per block where only two blocks fit a CU's LDS (T_det = 12: -2 us, T_det = 24: -10 us), four where three fit (T_det = 16: eight
         // were 9 us slower) - profiles/r5_encoder_nw_ab.txt
         const int nw = knobs().encp_nw ? (knobs().encp_nw == 4 ? 4 : 8) : (lds > 53 * 1024 ? 8 : 4);
-        const void* kern = fdt == SNN_FEAT_F16 ? encode_rows_perm_h_kernel<feat_f16>(rb, nw) : fdt == SNN_FEAT_BF16 ? encode_rows_perm_h_kernel<feat_bf16>(rb, nw)
-                           : rb == 16 ? (nw == 8 ? (const void*)k_encode_rows_perm<49, 16, 8> : (const void*)k_encode_rows_perm<49, 16, 4>)
-                                      : (nw == 8 ? (const void*)k_encode_rows_perm<49, 8, 8> : (const void*)k_encode_rows_perm<49, 8, 4>);
+        const void* kern = encode_rows_perm_kernel(rb, nw, fdt);
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         uint32_t* planes_f = (uint32_t*)((char*)ws + dp.o_enc);
@@ -2639,9 +2626,7 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
         const size_t lds = (size_t)fa.T * (7 + 8) * 4 * RW * 8;                  // word pairs + raw ballots
         for (int l = 0; l < n_levels; ++l)
             if (check_feat(levels_host[l].feat, fdt, "snn_det_head_forward_roialign")) return -1;
-        if (fdt == SNN_FEAT_F16) hipLaunchKernelGGL((k_roi_align_encode_perm_h<RW, feat_f16>), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
-        else if (fdt == SNN_FEAT_BF16) hipLaunchKernelGGL((k_roi_align_encode_perm_h<RW, feat_bf16>), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
-        else hipLaunchKernelGGL(k_roi_align_encode_perm<RW>, dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
+        launch_picked(roi_align_encode_perm_kernel<RW>(fdt), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
         SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
     } else if ((rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, dp.win.enc_steps, p,
                                            (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per, fdt))) {
