@@ -302,6 +302,36 @@ int snn_det_postprocess(const float* class_logits, const float* box_regression, 
                         float* all_scores, float* all_boxes, float* out_boxes, float* out_scores, int* out_labels,
                         int* out_counts, int out_cap, void* workspace, size_t workspace_bytes, snn_stream_t stream);
 
+/* ---- static-shape path: FPN features -> padded detections with no host synchronisation -------------
+ * snn_rpn_proposals already leaves [N][post_nms_top_n][4] padded rows and out_counts[N] in device memory.  The two calls below take
+ * that layout on: every per-image row count is READ ON THE DEVICE and clamped to 0 .. cap there (a garbage count never indexes out
+ * of bounds), shapes depend on (N, cap) alone, nothing waits for the host: the sequence snn_rpn_head_forward, snn_rpn_proposals,
+ * snn_roi_assign, snn_det_head_forward_roialign, snn_det_postprocess_padded runs from the FPN features to the detections on one stream.
+ * Bad arguments return -1 (limits: -4) before any device work.
+ *
+ * snn_roi_assign: the RoI table of snn_det_head_forward_roialign from padded proposals, one launch.  Row r = i * cap + j:
+ * roi_batch[r] = i; for j < clamp(counts[i], 0, cap) rois[r] = boxes[r] and roi_level[r] = torchvision's LevelMapper,
+ *   clamp(floor(canonical_level + log2(sqrt((x2 - x1) * (y2 - y1)) / canonical_scale) + 1e-6), k_min, k_max) - k_min
+ * in fp32 in that operation order (a zero-area box gives -inf and therefore k_min); the other rows are NOT read and become the box
+ * (0, 0, 0, 0) on level 0.  N <= 64, cap <= 10240, k_min <= k_max < k_min + 8, canonical_scale > 0 (the reference: 224, level 4). */
+int snn_roi_assign(const float* boxes /* [N][cap][4] */, const int* counts_dev /* [N] */, int N, int cap, int k_min, int k_max,
+                   float canonical_scale, float canonical_level, float* rois /* [N*cap][4] */, int32_t* roi_batch /* [N*cap] */,
+                   int32_t* roi_level /* [N*cap] */, snn_stream_t stream);
+
+/* snn_det_postprocess_padded: snn_det_postprocess for rows laid out [N][cap] (class_logits [N*cap][K], box_regression [N*cap][4K],
+ * proposals [N*cap][4]) with the rows per image in device memory; workspace snn_det_postprocess_workspace_bytes(N, cap, K).
+ * With c_i = clamp(roi_counts_dev[i], 0, cap): out_boxes / out_scores / out_labels / out_counts are bit-identical to snn_det_postprocess
+ * on the concatenation of the first c_i rows of every image (rois_per_image_host = c); all_scores [N*cap][K] / all_boxes [N*cap][K][4]
+ * are bit-identical on those rows and zero on the others; output rows behind the out_counts[2i] + out_counts[2i+1] rows of an image are
+ * zero.  Padding rows are never read.  cap <= 10240, (K-1) * min(detections_per_img, cap) <= 8192 (else -4), out_cap >=
+ * detections_per_img + cap.  Six launches. */
+int snn_det_postprocess_padded(const float* class_logits, const float* box_regression, const float* proposals,
+                               const int* roi_counts_dev /* [N] */, int N, int cap, int K, const float* image_hw_host,
+                               const float* box_weights_host, float score_thresh, float nms_thresh, int detections_per_img,
+                               float min_size, float* all_scores, float* all_boxes, float* out_boxes, float* out_scores,
+                               int* out_labels, int* out_counts, int out_cap, void* workspace, size_t workspace_bytes,
+                               snn_stream_t stream);
+
 /* ---- exchange payload of the data-parallel path: what each rank hands to the ONE all-gather of a batch (the reference's
  * counterpart is the pickled all_gather_object of coco_eval.py:158-177, disabled under NCCL at train.py:874-880).  Per
  * image the max_det RoIs with the highest foreground score (softmax over K, best class >= 1; the selection of

@@ -8,3 +8,4 @@ from .generalized_rcnn import GeneralizedRCNN     # noqa: F401
 from .model import create_model                   # noqa: F401
 from .pipeline import StreamPipeline             # noqa: F401
 from .sweep import timestep_sweep               # noqa: F401
+from .static import heads_padded, unpad       # noqa: F401

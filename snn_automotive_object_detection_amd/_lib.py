@@ -96,6 +96,12 @@ SYMBOLS = {
     "snn_det_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                       C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    # the static-shape path: per-image row counts read on the device
+    "snn_roi_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, c_stream]),
+    "snn_det_postprocess_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
     "snn_det_exchange_payload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            c_stream]),
     "snn_nms_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -173,6 +179,7 @@ SYMBOLS = {
 }
 
 _LIB = None
+_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded")
 
 
 class SnnHipError(RuntimeError):
@@ -205,8 +212,9 @@ def load(build_if_missing: bool = True):
                           "there is no CPU fallback" % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
-        if path != _build.LIB_PATH and name.endswith("_typed") and not hasattr(lib, name):
-            continue                     # an A/B library from before the typed entry points: fp32 features only (half features: AttributeError)
+        if path != _build.LIB_PATH and (name.endswith("_typed") or name in _STATIC_PATH) and not hasattr(lib, name):
+            continue                     # an A/B library from before the typed entry points: fp32 features only (half features: AttributeError);
+                                         # from before the static-shape path: the list API only
         fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -2288,6 +2288,72 @@ size_t snn_det_postprocess_workspace_bytes(int N, int max_rois_per_image, int K)
     return det_post_layout(N, K, max_rois_per_image, off);
 }
 
+// the launches of both entry points.  counts_dev = nullptr: compacted rows, a.roi_base[] filled (snn_det_postprocess); else rows [N][Rmax]
+// with the count of image i read from counts_dev[i] on the device, and the output rows behind the detections zeroed
+static int det_post_run(DetPostArgs& a, const int* counts_dev, float nms_thresh, float* out_boxes, float* out_scores, int* out_labels,
+                        int* out_counts, void* ws, size_t ws_bytes, hipStream_t s, const char* who) {
+    const int N = a.N, K = a.K, rmax = a.Rmax;
+    size_t off[9];
+    if (ws_bytes < det_post_layout(N, K, rmax, off)) return fail(-2, "%s: workspace too small", who);
+    char* w = (char*)ws;
+    a.boxes = (float*)(w + off[0]); a.skey = (float*)(w + off[1]);
+    a.s_boxes = (float*)(w + off[2]); a.s_score = (float*)(w + off[3]); a.s_roi = (int*)(w + off[4]); a.n_valid = (int*)(w + off[5]);
+    int* keep = (int*)(w + off[6]);
+    int* n_keep = (int*)(w + off[7]);
+    unsigned long long* mask = (unsigned long long*)(w + off[8]);
+    const int L = N * K;
+    if (counts_dev) {
+        hipLaunchKernelGGL(k_det_candidates_padded, dim3(cdiv(rmax, 256), L), dim3(256), 0, s, a, counts_dev);
+        SNN_CHECK_LAUNCH("k_det_candidates_padded");
+    } else {
+        hipLaunchKernelGGL(k_det_candidates, dim3(cdiv(rmax, 256), L), dim3(256), 0, s, a);
+        SNN_CHECK_LAUNCH("k_det_candidates");
+    }
+    int np2 = 1;
+    while (np2 < rmax) np2 <<= 1;
+    const size_t sort_lds = max((size_t)np2 * 8, (size_t)256);
+    hipError_t e = hipFuncSetAttribute((const void*)k_sort_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
+    if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    uint32_t* list_max = (uint32_t*)(a.n_valid + L);
+    hipLaunchKernelGGL(k_sort_lists, dim3(L), dim3(1024), sort_lds, s, a.skey, a.boxes, rmax, a.s_boxes, a.s_score, a.s_roi, a.n_valid, list_max);
+    SNN_CHECK_LAUNCH("k_sort_lists");
+    // NMS: one list per (image, class); a foreground class stops after detections_per_img kept boxes, the background list keeps all
+    NmsLists nl;
+    memset(&nl, 0, sizeof(nl));
+    const int wmax = cdiv(rmax, 64);
+    nl.boxes = a.s_boxes; nl.skey = nullptr; nl.n_dev = a.n_valid; nl.img_stride = (long long)K * rmax;
+    nl.mask_img = (long long)K * rmax * wmax; nl.L = K;
+    for (int c = 0; c < K; ++c) { nl.off[c] = c * rmax; nl.cap[c] = rmax; nl.moff[c] = (long long)c * rmax * wmax; }
+    nl.max_keep0 = rmax; nl.max_keep = a.det_per_img;
+    nl.trick_cnt = a.n_valid; nl.trick_max = list_max; nl.trick_c0 = 1;    // the foreground classes of an image are one batched_nms call
+    hipLaunchKernelGGL(k_nms_mask_lists, dim3(wmax, wmax, L), dim3(64), 0, s, nl, nms_thresh, mask);
+    SNN_CHECK_LAUNCH("k_nms_mask_lists");
+    const size_t lds = (size_t)2 * 64 * wmax * 8;
+    if (lds > 160 * 1024) return fail(-4, "%s: %d RoIs per image need %zu B of LDS for the NMS walk", who, rmax, lds);
+    e = hipFuncSetAttribute((const void*)k_nms_scan_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_nms_scan_lists, dim3(L), dim3(256), lds, s, nl, mask, keep, n_keep);
+    SNN_CHECK_LAUNCH("k_nms_scan_lists");
+    hipLaunchKernelGGL(k_det_merge, dim3(N), dim3(1024), 0, s, a, keep, n_keep, out_boxes, out_scores, out_labels, out_counts);
+    SNN_CHECK_LAUNCH("k_det_merge");
+    if (counts_dev) {
+        hipLaunchKernelGGL(k_det_zero_tail, dim3(cdiv(a.out_cap, 256), N), dim3(256), 0, s, out_counts, a.out_cap, out_boxes, out_scores, out_labels);
+        SNN_CHECK_LAUNCH("k_det_zero_tail");
+    }
+    return 0;
+}
+
+static void det_post_fill(DetPostArgs& a, const float* class_logits, const float* box_regression, const float* proposals, int N, int K,
+                          int rmax, const float* image_hw_host, const float* box_weights_host, float score_thresh, int detections_per_img,
+                          float min_size, float* all_scores, float* all_boxes, int out_cap) {
+    for (int i = 0; i < N; ++i) { a.img_h[i] = image_hw_host[2 * i]; a.img_w[i] = image_hw_host[2 * i + 1]; }
+    a.logits = class_logits; a.deltas = box_regression; a.props = proposals;
+    a.N = N; a.K = K; a.Rmax = rmax; a.det_per_img = detections_per_img; a.out_cap = out_cap;
+    a.score_thresh = score_thresh; a.min_size = min_size; a.clip = (float)4.135166556742356;
+    a.wx = box_weights_host[0]; a.wy = box_weights_host[1]; a.ww = box_weights_host[2]; a.wh = box_weights_host[3];
+    a.all_scores = all_scores; a.all_boxes = all_boxes;
+}
+
 int snn_det_postprocess(const float* class_logits, const float* box_regression, const float* proposals,
                         const int* rois_per_image_host, int N, int K, const float* image_hw_host,
                         const float* box_weights_host, float score_thresh, float nms_thresh, int detections_per_img,
@@ -2305,7 +2371,6 @@ int snn_det_postprocess(const float* class_logits, const float* box_regression, 
         if (rois_per_image_host[i] < 0) return fail(-1, "snn_det_postprocess: negative RoI count");
         a.roi_base[i + 1] = a.roi_base[i] + rois_per_image_host[i];
         rmax = max(rmax, rois_per_image_host[i]);
-        a.img_h[i] = image_hw_host[2 * i]; a.img_w[i] = image_hw_host[2 * i + 1];
     }
     if (rmax == 0) {
         if (hipMemsetAsync(out_counts, 0, sizeof(int) * 2 * N, (hipStream_t)stream) != hipSuccess) return fail(-3, "hipMemsetAsync failed");
@@ -2315,50 +2380,46 @@ int snn_det_postprocess(const float* class_logits, const float* box_regression, 
     if ((long long)(K - 1) * min(detections_per_img, rmax) > DET_MERGE_MAX)
         return fail(-4, "snn_det_postprocess: (K-1) * detections_per_img = %lld exceeds %d", (long long)(K - 1) * detections_per_img, DET_MERGE_MAX);
     if (out_cap < detections_per_img + rmax) return fail(-1, "snn_det_postprocess: out_cap %d < %d", out_cap, detections_per_img + rmax);
-    size_t off[9];
-    if (ws_bytes < det_post_layout(N, K, rmax, off)) return fail(-2, "snn_det_postprocess: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    a.logits = class_logits; a.deltas = box_regression; a.props = proposals;
-    a.N = N; a.K = K; a.Rmax = rmax; a.det_per_img = detections_per_img; a.out_cap = out_cap;
-    a.score_thresh = score_thresh; a.min_size = min_size; a.clip = (float)4.135166556742356;
-    a.wx = box_weights_host[0]; a.wy = box_weights_host[1]; a.ww = box_weights_host[2]; a.wh = box_weights_host[3];
-    a.all_scores = all_scores; a.all_boxes = all_boxes;
-    char* w = (char*)ws;
-    a.boxes = (float*)(w + off[0]); a.skey = (float*)(w + off[1]);
-    a.s_boxes = (float*)(w + off[2]); a.s_score = (float*)(w + off[3]); a.s_roi = (int*)(w + off[4]); a.n_valid = (int*)(w + off[5]);
-    int* keep = (int*)(w + off[6]);
-    int* n_keep = (int*)(w + off[7]);
-    unsigned long long* mask = (unsigned long long*)(w + off[8]);
-    const int L = N * K;
-    hipLaunchKernelGGL(k_det_candidates, dim3(cdiv(rmax, 256), L), dim3(256), 0, s, a);
-    SNN_CHECK_LAUNCH("k_det_candidates");
-    int np2 = 1;
-    while (np2 < rmax) np2 <<= 1;
-    const size_t sort_lds = max((size_t)np2 * 8, (size_t)256);
-    hipError_t e = hipFuncSetAttribute((const void*)k_sort_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sort_lds);
-    if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    uint32_t* list_max = (uint32_t*)(a.n_valid + L);
-    hipLaunchKernelGGL(k_sort_lists, dim3(L), dim3(1024), sort_lds, s, a.skey, a.boxes, rmax, a.s_boxes, a.s_score, a.s_roi, a.n_valid, list_max);
-    SNN_CHECK_LAUNCH("k_sort_lists");
-    // NMS: one list per (image, class); a foreground class stops after detections_per_img kept boxes, the background list keeps all
-    NmsLists nl;
-    memset(&nl, 0, sizeof(nl));
-    const int wmax = cdiv(rmax, 64);
-    nl.boxes = a.s_boxes; nl.skey = nullptr; nl.n_dev = a.n_valid; nl.img_stride = (long long)K * rmax;
-    nl.mask_img = (long long)K * rmax * wmax; nl.L = K;
-    for (int c = 0; c < K; ++c) { nl.off[c] = c * rmax; nl.cap[c] = rmax; nl.moff[c] = (long long)c * rmax * wmax; }
-    nl.max_keep0 = rmax; nl.max_keep = detections_per_img;
-    nl.trick_cnt = a.n_valid; nl.trick_max = list_max; nl.trick_c0 = 1;    // the foreground classes of an image are one batched_nms call
-    hipLaunchKernelGGL(k_nms_mask_lists, dim3(wmax, wmax, L), dim3(64), 0, s, nl, nms_thresh, mask);
-    SNN_CHECK_LAUNCH("k_nms_mask_lists");
-    const size_t lds = (size_t)2 * 64 * wmax * 8;
-    if (lds > 160 * 1024) return fail(-4, "snn_det_postprocess: %d RoIs per image need %zu B of LDS for the NMS walk", rmax, lds);
-    e = hipFuncSetAttribute((const void*)k_nms_scan_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_nms_scan_lists, dim3(L), dim3(256), lds, s, nl, mask, keep, n_keep);
-    SNN_CHECK_LAUNCH("k_nms_scan_lists");
-    hipLaunchKernelGGL(k_det_merge, dim3(N), dim3(1024), 0, s, a, keep, n_keep, out_boxes, out_scores, out_labels, out_counts);
-    SNN_CHECK_LAUNCH("k_det_merge");
+    det_post_fill(a, class_logits, box_regression, proposals, N, K, rmax, image_hw_host, box_weights_host, score_thresh, detections_per_img,
+                  min_size, all_scores, all_boxes, out_cap);
+    return det_post_run(a, nullptr, nms_thresh, out_boxes, out_scores, out_labels, out_counts, ws, ws_bytes, (hipStream_t)stream,
+                        "snn_det_postprocess");
+}
+
+#define DET_PADDED_MAX_ROIS 10240                 // 2 x 64 x ceil(cap / 64) x 8 B of LDS for the NMS walk <= 160 KB
+int snn_det_postprocess_padded(const float* class_logits, const float* box_regression, const float* proposals,
+                               const int* roi_counts_dev, int N, int cap, int K, const float* image_hw_host,
+                               const float* box_weights_host, float score_thresh, float nms_thresh, int detections_per_img,
+                               float min_size, float* all_scores, float* all_boxes, float* out_boxes, float* out_scores,
+                               int* out_labels, int* out_counts, int out_cap, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    if (!class_logits || !box_regression || !proposals || !roi_counts_dev || !image_hw_host || !box_weights_host || !all_scores ||
+        !all_boxes || !out_boxes || !out_scores || !out_labels || !out_counts || !ws)
+        return fail(-1, "snn_det_postprocess_padded: null argument");
+    if (N <= 0 || N > RPN_MAX_IMAGES || cap <= 0 || K < 2 || K > NMS_MAX_CAT || detections_per_img <= 0)
+        return fail(-1, "snn_det_postprocess_padded: bad argument (1 <= images <= %d, cap >= 1, 2 <= classes <= %d)", RPN_MAX_IMAGES, NMS_MAX_CAT);
+    if (cap > DET_PADDED_MAX_ROIS) return fail(-4, "snn_det_postprocess_padded: cap = %d rows per image (max %d)", cap, DET_PADDED_MAX_ROIS);
+    if ((long long)(K - 1) * min(detections_per_img, cap) > DET_MERGE_MAX)
+        return fail(-4, "snn_det_postprocess_padded: (K-1) * detections_per_img = %lld exceeds %d", (long long)(K - 1) * detections_per_img, DET_MERGE_MAX);
+    if (out_cap < detections_per_img + cap) return fail(-1, "snn_det_postprocess_padded: out_cap %d < %d", out_cap, detections_per_img + cap);
+    DetPostArgs a;
+    memset(&a, 0, sizeof(a));
+    det_post_fill(a, class_logits, box_regression, proposals, N, K, cap, image_hw_host, box_weights_host, score_thresh, detections_per_img,
+                  min_size, all_scores, all_boxes, out_cap);
+    return det_post_run(a, roi_counts_dev, nms_thresh, out_boxes, out_scores, out_labels, out_counts, ws, ws_bytes, (hipStream_t)stream,
+                        "snn_det_postprocess_padded");
+}
+
+// ---- RoI table of the fused RoIAlign encoder from padded proposals ---------------------------------
+int snn_roi_assign(const float* boxes, const int* counts_dev, int N, int cap, int k_min, int k_max, float canonical_scale,
+                   float canonical_level, float* rois, int* roi_batch, int* roi_level, snn_stream_t stream) {
+    if (!boxes || !counts_dev || !rois || !roi_batch || !roi_level) return fail(-1, "snn_roi_assign: null argument");
+    if (N <= 0 || N > RPN_MAX_IMAGES || cap <= 0 || cap > DET_PADDED_MAX_ROIS)
+        return fail(-1, "snn_roi_assign: bad argument (1 <= images <= %d, 1 <= cap <= %d)", RPN_MAX_IMAGES, DET_PADDED_MAX_ROIS);
+    if (k_min > k_max || k_max - k_min >= SNN_MAX_LEVELS || !(canonical_scale > 0.0f))
+        return fail(-1, "snn_roi_assign: bad level range (k_min <= k_max < k_min + %d, canonical_scale > 0)", SNN_MAX_LEVELS);
+    hipLaunchKernelGGL(k_roi_assign, dim3(cdiv((long long)N * cap, 256)), dim3(256), 0, (hipStream_t)stream, boxes, counts_dev, N, cap,
+                       k_min, k_max, canonical_scale, canonical_level, rois, roi_batch, roi_level);
+    SNN_CHECK_LAUNCH("k_roi_assign");
     return 0;
 }
 

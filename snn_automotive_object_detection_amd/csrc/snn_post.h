@@ -636,14 +636,9 @@ struct DetPostArgs {
     float* s_boxes; float* s_score; int* s_roi; int* n_valid;   // sorted
 };
 
-__global__ __launch_bounds__(256) void k_det_candidates(const DetPostArgs a) {
-    const int list = blockIdx.y, img = list / a.K, k = list % a.K, bg = k == 0;
-    const int rl = blockIdx.x * 256 + threadIdx.x;
-    if (rl >= a.Rmax) return;
-    const int Ri = a.roi_base[img + 1] - a.roi_base[img];
-    const size_t o = (size_t)list * a.Rmax + rl;
-    if (rl >= Ri) { a.skey[o] = -1.0f; reinterpret_cast<float4*>(a.boxes)[o] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-    const int r = a.roi_base[img] + rl;
+// class k of RoI row r (image img) -> candidate slot o of its list, and its entries of all_scores / all_boxes
+__device__ __forceinline__ void det_candidate(const DetPostArgs& a, int img, int k, int r, size_t o) {
+    const bool bg = k == 0;
     const float* lg = a.logits + (size_t)r * a.K;
     float mx = lg[0];
     for (int j = 1; j < a.K; ++j) mx = fmaxf(mx, lg[j]);
@@ -671,6 +666,36 @@ __global__ __launch_bounds__(256) void k_det_candidates(const DetPostArgs a) {
     const bool valid = big && (bg ? !has_fg_cand : score > a.score_thresh);
     reinterpret_cast<float4*>(a.boxes)[o] = make_float4(x1, y1, x2, y2);
     a.skey[o] = valid ? score : -1.0f;
+}
+
+__global__ __launch_bounds__(256) void k_det_candidates(const DetPostArgs a) {
+    const int list = blockIdx.y, img = list / a.K, k = list % a.K;
+    const int rl = blockIdx.x * 256 + threadIdx.x;
+    if (rl >= a.Rmax) return;
+    const int Ri = a.roi_base[img + 1] - a.roi_base[img];
+    const size_t o = (size_t)list * a.Rmax + rl;
+    if (rl >= Ri) { a.skey[o] = -1.0f; reinterpret_cast<float4*>(a.boxes)[o] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
+    det_candidate(a, img, k, a.roi_base[img] + rl, o);
+}
+
+// the same for rows laid out [N][Rmax] (the static-shape path): image img owns rows img * Rmax + [0, Rmax), of which
+// the first clamp(counts[img], 0, Rmax) are RoIs.  The padding rows are never read; their candidate slots carry key -1 like the slots
+// past the end of a short image above, and their all_scores / all_boxes entries are written as zeros (a.roi_base is not used).
+__global__ __launch_bounds__(256) void k_det_candidates_padded(const DetPostArgs a, const int* __restrict__ counts) {
+    const int list = blockIdx.y, img = list / a.K, k = list % a.K;
+    const int rl = blockIdx.x * 256 + threadIdx.x;
+    if (rl >= a.Rmax) return;
+    const int Ri = min(max(counts[img], 0), a.Rmax);
+    const size_t o = (size_t)list * a.Rmax + rl;
+    const int r = img * a.Rmax + rl;
+    if (rl >= Ri) {
+        a.skey[o] = -1.0f;
+        reinterpret_cast<float4*>(a.boxes)[o] = make_float4(0.f, 0.f, 0.f, 0.f);
+        a.all_scores[(size_t)r * a.K + k] = 0.0f;
+        reinterpret_cast<float4*>(a.all_boxes)[(size_t)r * a.K + k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    det_candidate(a, img, k, r, o);
 }
 
 // one block per list: order = decreasing (score, then lower slot); n_valid = candidates with score >= 0
@@ -782,6 +807,43 @@ __global__ __launch_bounds__(1024) void k_det_merge(const DetPostArgs a, const i
         out_labels[dst] = 0;
     }
     if (tid == 0) { out_counts[2 * img] = n_fg; out_counts[2 * img + 1] = n_bg; }
+}
+
+// static-shape path: the rows of out_* [N][out_cap] behind the fg + bg rows k_det_merge wrote -> zero (the outputs of a replayed graph
+// then depend on the inputs alone)
+__global__ __launch_bounds__(256) void k_det_zero_tail(const int* __restrict__ out_counts, int out_cap, float* __restrict__ out_boxes,
+                                                       float* __restrict__ out_scores, int* __restrict__ out_labels) {
+    const int img = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= out_cap || r < out_counts[2 * img] + out_counts[2 * img + 1]) return;
+    const size_t dst = (size_t)img * out_cap + r;
+    reinterpret_cast<float4*>(out_boxes)[dst] = make_float4(0.f, 0.f, 0.f, 0.f);
+    out_scores[dst] = 0.0f;
+    out_labels[dst] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// RoI table of the fused RoIAlign encoder from padded proposals [N][cap][4] + device-side counts, one launch: torchvision's
+// LevelMapper (stock/roi_align.py:97-99, fp32, that operation order) and the image index per row; rows at or past
+// clamp(counts[img], 0, cap) become the box (0, 0, 0, 0) on level 0 without being read.  A zero-area box gives log2(0) = -inf -> k_min;
+// a NaN (x2 < x1 on one axis only) fails both comparisons of the clamp and lands on k_min as well: the level is always a valid index.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_roi_assign(const float* __restrict__ boxes, const int* __restrict__ counts, int N, int cap,
+                                                    int k_min, int k_max, float canonical_scale, float canonical_level,
+                                                    float* __restrict__ rois, int* __restrict__ roi_batch, int* __restrict__ roi_level) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= N * cap) return;
+    const int img = row / cap, rl = row - img * cap;
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    int lvl = 0;
+    if (rl < min(max(counts[img], 0), cap)) {
+        b = reinterpret_cast<const float4*>(boxes)[row];
+        const float s = sqrtf(__fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y)));
+        const float v = floorf(__fadd_rn(__fadd_rn(canonical_level, log2f(__fdiv_rn(s, canonical_scale))), 1e-6f));
+        lvl = (int)fminf(fmaxf(v, (float)k_min), (float)k_max) - k_min;
+    }
+    reinterpret_cast<float4*>(rois)[row] = b;
+    roi_batch[row] = img;
+    roi_level[row] = lvl;
 }
 
 // impulse responses of the LI cell (norse leaky_integrator.py: li_feed_forward_step; v_leak = 0)

@@ -111,10 +111,13 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         return self._finish(out)
 
     @torch.no_grad()
-    def forward_roialign(self, feats, scales, rois, roi_level):
+    def forward_roialign(self, feats, scales, rois, roi_level, roi_batch=None):
         """Same head fed straight from the FPN maps: MultiScaleRoIAlign(7x7, sampling 2) is fused with the encoder
-        (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2)."""
-        out = ops.det_head_forward_roialign(feats, scales, rois[:, 1:5], rois[:, 0], roi_level, T=int(self.num_steps),
+        (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2) - or, with
+        ``roi_batch`` (int32 [R], the image of every row: the table ops.roi_assign writes), rois [R,4]."""
+        if roi_batch is None:
+            rois, roi_batch = rois[:, 1:5], rois[:, 0]
+        out = ops.det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, T=int(self.num_steps),
                                             **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]))
         return self._finish(out)
 

@@ -37,6 +37,41 @@ class GeneralizedRCNN(nn.Module):
         detections, _ = self.roi_heads(features, proposals, images.image_sizes, targets)   # :118
         return self.finish_detections(detections, proposal_extras, images.image_sizes, original_image_sizes)
 
+    @torch.no_grad()
+    def forward_padded(self, images: List[Tensor]) -> Dict[str, Tensor]:
+        """``forward`` with fixed shapes: transform -> backbone -> static.heads_padded (both heads, proposal selection,
+        RoI assignment, detection post-processing: no host synchronisation from the FPN features on) -> boxes / all_boxes / proposals
+        back in the original image sizes.  Returns the dict of padded tensors static.heads_padded documents; ``static.unpad`` turns it
+        into what ``forward`` returns, with the one host synchronisation.  ``rois`` stay in the coordinates of the resized images."""
+        from . import static
+        if self.training:
+            raise NotImplementedError("inference only (call .eval()): training is out of scope (DESIGN.md §7)")
+        original_image_sizes = [(int(img.shape[-2]), int(img.shape[-1])) for img in images]
+        images, _ = self.transform(images, None)
+        features = self.backbone(images.tensors)
+        if isinstance(features, torch.Tensor):
+            features = OrderedDict([("0", features)])
+        out = static.heads_padded(self, features, images)
+        scale = self._resize_ratios(images.image_sizes, original_image_sizes, out["boxes"].device)      # [N, 1, 4]: (rw, rh, rw, rh)
+        out["boxes"] = out["boxes"] * scale
+        out["all_boxes"] = out["all_boxes"] * scale[:, :, None, :]
+        out["proposals"] = out["proposals"] * scale
+        return out
+
+    def _resize_ratios(self, image_sizes, original_image_sizes, device) -> Tensor:
+        """resize_boxes' ratios (fp32 new / old, as it forms them) of every image as one device tensor; uploaded once per set of sizes"""
+        cache = self.__dict__.setdefault("_ratio_cache", {})
+        key = (tuple(map(tuple, image_sizes)), tuple(map(tuple, original_image_sizes)), str(device))
+        if key not in cache:
+            if len(cache) >= 64:
+                cache.clear()
+            rows = []
+            for im_s, o_im_s in zip(image_sizes, original_image_sizes):
+                rh, rw = [torch.tensor(orig, dtype=torch.float32) / torch.tensor(resized, dtype=torch.float32) for orig, resized in zip(o_im_s, im_s)]
+                rows.append(torch.stack((rw, rh, rw, rh)))
+            cache[key] = torch.stack(rows)[:, None, :].to(device)
+        return cache[key]
+
     def finish_detections(self, detections, proposal_extras, image_sizes, original_image_sizes):
         """the end of ``forward`` (generalized_rcnn.py:119-132): back to the original sizes, the RPN's extras merged in"""
         detections = self.transform.postprocess(detections, image_sizes, original_image_sizes)

@@ -874,6 +874,23 @@ def nms_keep_mask(boxes: torch.Tensor, scores: torch.Tensor, idxs: Optional[torc
     return order, kept[:n]
 
 
+_ANCHORS_HOST = {}                           # (storage address, version, device, shape) -> (the anchor tensor, its values as fp32 on the host)
+
+
+def _anchors_host(base: torch.Tensor):
+    """the cell anchors of a level as nested lists of Python floats (their fp32 values).  The copy to the host is a synchronisation when the
+    anchors live on the device, so it is made once per anchor tensor: the entry holds the tensor (its storage cannot be reused by another
+    one while it is cached) and is keyed on the version counter (in-place edits make a new entry).  Assumes what AnchorGenerator does: the
+    cell anchors are built once and never edited through ``.data`` / ``set_``, which would not bump the version counter"""
+    key = (base.data_ptr(), base._version, str(base.device), base.dtype, tuple(base.shape))
+    hit = _ANCHORS_HOST.get(key)
+    if hit is None:
+        if len(_ANCHORS_HOST) >= 64:
+            _ANCHORS_HOST.clear()
+        hit = _ANCHORS_HOST[key] = (base, base.detach().cpu().to(torch.float32).tolist())
+    return hit[1]
+
+
 def rpn_proposals(logits: Sequence[torch.Tensor], deltas: Sequence[torch.Tensor], level_hw, strides, base_anchors,
                   image_sizes, pre_nms_top_n: int, post_nms_top_n: int, nms_thresh: float, score_thresh: float,
                   min_size: float, want_pre: bool = True):
@@ -897,10 +914,10 @@ def rpn_proposals(logits: Sequence[torch.Tensor], deltas: Sequence[torch.Tensor]
             raise _lib.SnnHipError("rpn_proposals: level %d has shapes %s / %s" % (l, tuple(lo.shape), tuple(de.shape)))
         lv[l].logits, lv[l].deltas, lv[l].H, lv[l].W = lo.data_ptr(), de.data_ptr(), H, W
         lv[l].stride_h, lv[l].stride_w = float(strides[l][0]), float(strides[l][1])
-        ba = base_anchors[l].detach().cpu().to(torch.float32)
+        ba = _anchors_host(base_anchors[l])
         for a in range(A):
             for q in range(4):
-                lv[l].base_anchors[a][q] = float(ba[a, q])
+                lv[l].base_anchors[a][q] = ba[a][q]
     K = lib.snn_rpn_proposals_candidates(lv, L, A, int(pre_nms_top_n))
     if K <= 0:
         raise _lib.SnnHipError("rpn_proposals: bad level description")
@@ -956,6 +973,67 @@ def det_postprocess(class_logits: torch.Tensor, box_regression: torch.Tensor, pr
 
 
 # ---------------------------------------------------------------------------------------------
+# the static-shape path: per-image row counts stay in device memory, shapes depend on (N, cap) alone
+# ---------------------------------------------------------------------------------------------
+def roi_assign(boxes: torch.Tensor, counts: torch.Tensor, k_min: int, k_max: int, canonical_scale: float = 224.0,
+               canonical_level: float = 4.0):
+    """RoI table of det_head_forward_roialign from padded proposals, one launch and no host synchronisation.
+    boxes [N, cap, 4] fp32, counts [N] int32 (device; clamped to 0 .. cap by the kernel) ->
+    (rois [N*cap, 4], roi_batch [N*cap] int32 = row // cap, roi_level [N*cap] int32 = torchvision's LevelMapper - k_min);
+    rows at or past the count of their image are the box (0, 0, 0, 0) on level 0."""
+    lib = _lib.load()
+    _need_gpu(boxes, "boxes")
+    _need_gpu(counts, "counts")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or tuple(counts.shape) != (boxes.shape[0],):
+        raise _lib.SnnHipError("roi_assign: boxes [N, cap, 4] and counts [N] expected, got %s and %s" % (tuple(boxes.shape), tuple(counts.shape)))
+    N, cap = boxes.shape[0], boxes.shape[1]
+    b, c = _f32c(boxes), counts.detach().to(torch.int32).contiguous()
+    rois = torch.empty((N * cap, 4), dtype=torch.float32, device=boxes.device)
+    roi_batch = torch.empty((N * cap,), dtype=torch.int32, device=boxes.device)
+    roi_level = torch.empty((N * cap,), dtype=torch.int32, device=boxes.device)
+    _lib.check(lib.snn_roi_assign(_ptr(b), _ptr(c), N, cap, int(k_min), int(k_max), float(canonical_scale), float(canonical_level),
+                                  _ptr(rois), _ptr(roi_batch), _ptr(roi_level), _stream()), "snn_roi_assign")
+    return rois, roi_batch, roi_level
+
+
+def det_postprocess_padded(class_logits: torch.Tensor, box_regression: torch.Tensor, proposals: torch.Tensor, counts: torch.Tensor,
+                           image_sizes, box_weights, score_thresh: float, nms_thresh: float, detections_per_img: int,
+                           min_size: float = 1e-2):
+    """det_postprocess for rows laid out [N, cap] with the rows per image in device memory: six launches, no host synchronisation.
+    class_logits [N*cap, K], box_regression [N*cap, 4K], proposals [N*cap, 4] (or [N, cap, 4]), counts [N] int32 (device; clamped to
+    0 .. cap by the kernels).  Returns (boxes [N, D, 4], scores [N, D], labels [N, D] int32, counts [N, 2] int32 (fg, bg),
+    all_scores [N*cap, K], all_boxes [N*cap, K, 4]) with D = detections_per_img + cap: the valid rows are bit-identical to
+    det_postprocess on the compacted rows, every other row is zero."""
+    lib = _lib.load()
+    dev = class_logits.device
+    N, K, R = len(image_sizes), class_logits.shape[1], class_logits.shape[0]
+    proposals = proposals.reshape(-1, 4)
+    if N <= 0 or R % N or R == 0 or tuple(box_regression.shape) != (R, 4 * K) or tuple(proposals.shape) != (R, 4) or tuple(counts.shape) != (N,):
+        raise _lib.SnnHipError("det_postprocess_padded: class_logits %s for %d images needs box_regression [R, %d], proposals [R, 4] and "
+                               "counts [%d] (got %s, %s, %s)" % (tuple(class_logits.shape), N, 4 * K, N, tuple(box_regression.shape),
+                                                                tuple(proposals.shape), tuple(counts.shape)))
+    _need_gpu(class_logits, "class logits")
+    _need_gpu(counts, "counts")
+    cap = R // N
+    lg, dl, pr, cn = _f32c(class_logits), _f32c(box_regression), _f32c(proposals), counts.detach().to(torch.int32).contiguous()
+    D = int(detections_per_img) + cap
+    boxes = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((N, D), dtype=torch.float32, device=dev)
+    labels = torch.empty((N, D), dtype=torch.int32, device=dev)
+    out_counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    all_scores = torch.empty((R, K), dtype=torch.float32, device=dev)
+    all_boxes = torch.empty((R, K, 4), dtype=torch.float32, device=dev)
+    hw = (C.c_float * (2 * N))(*[float(v) for s in image_sizes for v in (s[0], s[1])])
+    ws = _WS.get(dev, max(1, lib.snn_det_postprocess_workspace_bytes(N, cap, K)))
+    bw = (C.c_float * 4)(*[float(v) for v in box_weights])
+    _lib.check(lib.snn_det_postprocess_padded(_ptr(lg), _ptr(dl), _ptr(pr), _ptr(cn), N, cap, K, hw, bw, float(score_thresh),
+                                              float(nms_thresh), int(detections_per_img), float(min_size), _ptr(all_scores),
+                                              _ptr(all_boxes), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(out_counts), D, _ptr(ws),
+                                              ws.numel(), _stream()), "snn_det_postprocess_padded")
+    return boxes, scores, labels, out_counts, all_scores, all_boxes
+
+
+# ---------------------------------------------------------------------------------------------
 # device guard: every wrapper above launches on "the current stream of the current device"; a caller holding tensors on
 # another GPU of the process (cuda:1 while cuda:0 is current) gets that device made current for the call, as torch's
 # own operators do
@@ -990,6 +1068,6 @@ for _name in ("pack_conv3x3", "pack_linear", "pack_heads", "pack_conv3x3_bf16x3"
               "conv3x3_lif_mx", "spike_conv3x3_mx", "conv3x3_lif_bf16x3", "spike_conv3x3_bf16x3", "affine_act_nchw", "encode_nchw", "encode_rows",
               "conv3x3_lif", "spike_gemm", "lif_scan", "det_exchange_payload", "li_heads", "rpn_head_forward", "det_head_forward",
               "det_rates", "roi_align_encode", "det_head_forward_roialign", "batched_nms", "nms_keep_mask", "rpn_proposals",
-              "det_postprocess"):
+              "det_postprocess", "roi_assign", "det_postprocess_padded"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

@@ -139,6 +139,47 @@ class RoIHeadsSNN(nn.Module):
             head_out = head(box_features)                                            # roi_heads.py:1230 (HIP)
         return self.detections_from_head(head_out, proposals, image_shapes)
 
+    @torch.no_grad()
+    def forward_padded(self, features: Dict[str, Tensor], boxes: Tensor, counts: Tensor, image_shapes: List[Tuple[int, int]]) -> Dict[str, Tensor]:
+        """``forward`` on padded proposals with no host synchronisation: boxes [N, cap, 4], counts [N] int32 in device
+        memory (RegionProposalNetwork.proposals_padded) -> a dict of fixed-shape tensors, D = detections_per_img + cap:
+        boxes [N, D, 4], scores [N, D], labels [N, D] int32 (per image counts[i, 0] foreground detections, then counts[i, 1] background
+        boxes, then zeros), counts [N, 2], all_scores [N, cap, K], all_boxes [N, cap, K, 4] (zero at or past roi_counts[i]),
+        rois [N, cap, 4] (the proposals, padding zeroed), roi_counts [N] (counts clamped to 0 .. cap), and the head's own outputs on
+        every row, padding included: class_logits [N*cap, K], box_regression [N*cap, 4K] (what the detections were computed from).
+        ops.roi_assign -> the fused RoIAlign head on all N * cap rows -> ops.det_postprocess_padded: the padding rows go through the
+        head and are ignored.  Nothing falls back: NotImplementedError for training / spike-rate mode / only_one_bbox, ValueError with the
+        reason for ``post`` != "hip", a pool or head the fused RoIAlign path does not take, a shape outside snn_det_postprocess' limits."""
+        from . import ops
+        pool, head = self.box_roi_pool, self.box_head_and_predictor
+        if self.training:
+            raise NotImplementedError("inference only: training the RoI heads is out of scope (DESIGN.md §7)")
+        if getattr(head, "spike_rates", False):
+            raise NotImplementedError("forward_padded: spike-rate mode returns rates, not detections - use forward()")
+        if getattr(head, "only_one_bbox", False):
+            raise NotImplementedError("forward_padded: only_one_bbox heads are not supported past the head (SURVEY.md appendix C.6)")
+        if self.post != "hip":
+            raise ValueError("forward_padded: post = %r (only \"hip\" writes padded detections)" % (self.post,))
+        if not self._fuses_roi_align("forward_roialign"):
+            raise ValueError("forward_padded: needs the fused RoIAlign head path (fuse_roi_align, a head with forward_roialign, "
+                             "a 7x7 sampling-2 MultiScaleRoIAlign pool)")
+        if boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.shape[0] != len(image_shapes):
+            raise ValueError("forward_padded: boxes [N, cap, 4] for %d images expected, got %s" % (len(image_shapes), tuple(boxes.shape)))
+        N, cap, K = boxes.shape[0], boxes.shape[1], head.num_classes
+        why = self._hip_postprocess_refusal(N, cap, K) if cap > 0 else "cap = 0 rows per image"
+        if why is not None:
+            raise ValueError("forward_padded: %s" % why)
+        feats, scales, k_min, k_max = pool.levels(features, image_shapes)
+        rois, roi_batch, roi_level = ops.roi_assign(boxes, counts, k_min, k_max, pool.canonical_scale, pool.canonical_level)
+        class_logits, box_regression = head.forward_roialign(feats, scales, rois, roi_level, roi_batch)
+        out_boxes, scores, labels, out_counts, all_scores, all_boxes = ops.det_postprocess_padded(
+            class_logits, box_regression, rois, counts, image_shapes, self.box_coder.weights, self.score_thresh, self.nms_thresh,
+            self.detections_per_img)
+        return {"boxes": out_boxes, "scores": scores, "labels": labels, "counts": out_counts,
+                "all_scores": all_scores.view(N, cap, K), "all_boxes": all_boxes.view(N, cap, K, 4),
+                "rois": rois.view(N, cap, 4), "roi_counts": counts.clamp(0, cap),
+                "class_logits": class_logits, "box_regression": box_regression}
+
     def head_readouts(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]], steps) -> dict:
         """the head call of ``forward`` with a readout per T_det of ``steps`` (one pass at steps[-1]; the fused RoIAlign path where
         ``forward`` takes it): {T_det: head output}"""

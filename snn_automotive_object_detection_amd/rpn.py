@@ -372,7 +372,9 @@ class RegionProposalNetwork(nn.Module):
             return "%d pre-NMS candidates per image (HIP path: <= 8192)" % k
         return None
 
-    def _proposals_hip(self, objectness, pred_bbox_deltas, images, feats):
+    def _rpn_proposals(self, objectness, pred_bbox_deltas, images):
+        """ops.rpn_proposals on the head's outputs: (boxes [N, post, 4], scores, counts [N] int32, pre-NMS boxes, pre-NMS objectness),
+        everything in device memory"""
         from . import ops
         N = objectness[0].shape[0]
         A = objectness[0].shape[1]
@@ -385,13 +387,35 @@ class RegionProposalNetwork(nn.Module):
             dl.append(d.detach().permute(0, 2, 3, 1).reshape(N * H * W, 4 * A))
             hw.append((H, W))
             strides.append((image_size[0] // H, image_size[1] // W))
-        boxes, scores, counts, pre_b, pre_p = ops.rpn_proposals(
+        return ops.rpn_proposals(
             lg, dl, hw, strides, self.anchor_generator.cell_anchors, images.image_sizes, self.pre_nms_top_n(),
             self.post_nms_top_n(), self.nms_thresh, self.score_thresh, self.min_size)
+
+    def _proposals_hip(self, objectness, pred_bbox_deltas, images, feats):
+        N = objectness[0].shape[0]
+        boxes, scores, counts, pre_b, pre_p = self._rpn_proposals(objectness, pred_bbox_deltas, images)
         cnt = counts.tolist()                                                          # the one host synchronisation
         final = [boxes[i, :c] for i, c in enumerate(cnt)]
         pre_nms = [{"proposals": pre_b[i], "objectness": pre_p[i]} for i in range(N)]
         return final, pre_nms
+
+    def proposals_padded(self, images, feats, head_out):
+        """``proposals_from_head`` without its host synchronisation: (boxes [N, cap, 4], counts [N] int32, extras) with
+        cap = post_nms_top_n, rows at or past counts[i] zero, extras = {"proposals" [N, Kc, 4], "objectness" [N, Kc]: the pre-NMS report,
+        "scores" [N, cap]}.  Only snn_rpn_proposals runs here: a configuration it does not take raises instead of falling back to
+        the stock ops (NotImplementedError: training / spike-rate mode; ValueError: ``post`` != "hip", a shape outside its limits)."""
+        if self.training:
+            raise NotImplementedError("inference only: training the RPN is out of scope (DESIGN.md §7)")
+        if len(head_out) == 3 or getattr(self.head, "spike_rates", False):
+            raise NotImplementedError("proposals_padded: spike-rate mode returns rates, not detections - use forward()")
+        objectness, pred_bbox_deltas = head_out[:2]
+        if self.post != "hip":
+            raise ValueError("proposals_padded: post = %r (only \"hip\" leaves padded proposals and counts on the device)" % (self.post,))
+        why = self._hip_proposals_refusal(objectness)
+        if why is not None:
+            raise ValueError("proposals_padded: %s" % why)
+        boxes, scores, counts, pre_b, pre_p = self._rpn_proposals(objectness, pred_bbox_deltas, images)
+        return boxes, counts, {"proposals": pre_b, "objectness": pre_p, "scores": scores}
 
     def forward(self, images, features, targets=None):
         if self.training:
