@@ -456,6 +456,19 @@ int snn_spike_conv3x3_bf16x3(const uint32_t* enc, size_t enc_stride_words, const
  *     enqueues NOTHING; the caller widens the features to fp32 and calls again with SNN_FEAT_F32. */
 enum { SNN_FEAT_F32 = 0, SNN_FEAT_F16 = 1, SNN_FEAT_BF16 = 2 };
 #define SNN_STATUS_NO_TYPED_KERNEL 1
+/* ---- channels-last (NHWC) feature maps ---------------------------------------------------------------------------------------------------
+ * SNN_FEAT_NHWC is a LAYOUT bit, OR-ed into the feat_dtype of the typed entries that read feature MAPS (both snn_rpn_head_forward_*_typed,
+ * both snn_det_head_forward_roialign_*_typed, snn_encode_nchw_typed).  With the bit every `feat` pointer of the call addresses [N][H][W][C]
+ * elements of the dtype in the low bits - what data_ptr() of a dense channels-last [N, C, H, W] tensor addresses.  The layout is per call, not
+ * per level; struct layouts and workspace sizes are unchanged, and the call returns bit for bit what it returns for the same values in NCHW.
+ *   - alignment: an NHWC base pointer must be 16-byte aligned for EVERY dtype, else -1;
+ *   - the row-fed entries (snn_det_head_forward_k_typed, snn_det_head_forward_readouts_typed) return -1 with the bit: pooled rows have no layout;
+ *   - snn_roi_align_encode_typed returns SNN_STATUS_NO_TYPED_KERNEL with the bit (flatten-order planes are not built for NHWC);
+ *   - NHWC kernels exist for C % 32 == 0 (the level / stage encoders) and, for the RoIAlign-fed detector head, for the plans in which fc6 reads
+ *     bin-major period planes (w6_inner == 49, word-major planes, threshold-form encoder, C % 64 == 0, SNN_ROI_TAB != 0).  Any other plan returns
+ *     SNN_STATUS_NO_TYPED_KERNEL with nothing enqueued; the caller converts the maps to NCHW and calls again without the bit.
+ * Without the bit SNN_FEAT_* behave exactly as before. */
+#define SNN_FEAT_NHWC 16
 int snn_rpn_head_forward_stages_typed(const snn_rpn_level* levels_host, int feat_dtype, int n_levels, int C, int A, int T,
                                       const snn_params* p_host, const void* w_shared_packed, const float* w_heads_packed,
                                       float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,

@@ -13,6 +13,7 @@ c_stream = C.c_void_p
 SNN_MAX_LEVELS = 8
 SNN_MAX_STEPS = 32
 FEAT_DTYPES = {"f32": 0, "f16": 1, "bf16": 2}          # SNN_FEAT_*
+FEAT_NHWC = 16                                            # SNN_FEAT_NHWC: layout bit, OR-ed into a FEAT_DTYPES code (channels-last maps)
 NO_TYPED_KERNEL = 1                                       # SNN_STATUS_NO_TYPED_KERNEL: nothing was enqueued; widen and call with "f32"
 PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3, "bf16": 4}
 

@@ -34,7 +34,15 @@ template <typename FT> __device__ __forceinline__ float feat_widen_bits(uint32_t
 // planes e_n, n > nd, leave COMPRESSED - the four dwords per (row, 64 k) k_compress_planes would make of them (primary occupancy, index
 // halves, secondary occupancy), computed from the block's words while they are in LDS - and their raw words are not written at all:
 // one launch and a 32-MB write + 32-MB read less per head (k_compress_planes stays for the stage-level entry points and the linear layers).
-template <int EM, typename FT>
+// NHWC (SNN_FEAT_NHWC; C % 32 == 0): `feat` addresses channels-last elements [N][HW][C] and only the LOAD phase differs - a thread's 32 channels
+// are one contiguous run (128 bytes fp32, 64 bytes half), so the block copies its 64 positions x 4 words with coalesced 16-byte loads (a position's
+// four words are one 512- / 256-byte run; a wave instruction reads whole runs, 1 KB) into LDS, as K1b' does (word pitch + 4 dwords: the
+// ds_read_b128 of a wave are conflict-free), and every thread picks its word up from there.  The per-thread alternative - 8 / 4 16-byte loads off
+// feat + ((n HW + pos) C + 32 cg) - touches 64 lines per instruction for 16 bytes each.  The tile lives in the dynamic LDS the plane words use
+// afterwards (a barrier in between); the launch sizes it ENC_NHWC_LDS_BYTES.  From x[0..31] on the text is the one of the NCHW form.
+#define ENC_NHWC_PITCH(FT) (32 * (int)sizeof(FT) / 4 + 4)                          // dwords per staged channel word
+#define ENC_NHWC_LDS_BYTES(T, esz) (ENC_LDS_BYTES(T) > (size_t)ENC_PB * ENC_WB * (32 * (esz) + 16) ? ENC_LDS_BYTES(T) : (size_t)ENC_PB * ENC_WB * (32 * (esz) + 16))
+template <int EM, typename FT, bool NHWC = false>
 __device__ __forceinline__ void encode_block(const FT* __restrict__ feat, int C, int HW, int Cw, int T, const NeuronP& p,
                                              const EncTh& eth, uint32_t* __restrict__ planes, size_t plane_stride, int n, int bx, int by,
                                              int Wpad = 0, size_t wm_rows = 0, uint32_t* __restrict__ cmp = nullptr, int nd = 0) {
@@ -48,7 +56,34 @@ __device__ __forceinline__ void encode_block(const FT* __restrict__ feat, int C,
     const int pos = bx * ENC_PB + pl;
     const int cg = by * ENC_WB + cgl;
     float x[32], v[32];
-    if (cg * 32 + 32 <= C) {
+    if constexpr (NHWC) {
+        constexpr int EPP = 16 / (int)sizeof(FT), PPW = 32 / EPP, PITCH = ENC_NHWC_PITCH(FT);     // elements per 16-byte piece, pieces per word
+        extern __shared__ __attribute__((aligned(16))) uint32_t tile[];                             // [4 words][64 positions][PITCH] (the bytes of wbuf)
+        const int nwb = min(ENC_WB, Cw - by * ENC_WB);                                              // channel words of this block
+        const FT* src = feat + ((size_t)n * HW + (size_t)bx * ENC_PB) * C + by * (ENC_WB * 32);
+#pragma unroll
+        for (int j = 0; j < PPW; ++j) {
+            // piece q of the block: position q / (4 PPW), then the position's run of 4 PPW pieces in address order
+            const int q = threadIdx.x + 256 * j, pq = q / (ENC_WB * PPW), rq = q % (ENC_WB * PPW), wq = rq / PPW;
+            u32x4 d = {0u, 0u, 0u, 0u};
+            if (bx * ENC_PB + pq < HW && wq < nwb) d = *reinterpret_cast<const u32x4*>(src + (size_t)pq * C + rq * EPP);
+            *reinterpret_cast<u32x4*>(tile + (wq * ENC_PB + pq) * PITCH + (rq % PPW) * 4) = d;
+        }
+        __syncthreads();
+        const uint32_t* mine = tile + (cgl * ENC_PB + pl) * PITCH;
+#pragma unroll
+        for (int k = 0; k < PPW; ++k) {
+            const u32x4 d = *reinterpret_cast<const u32x4*>(mine + 4 * k);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if constexpr (sizeof(FT) == 4) x[4 * k + r] = __uint_as_float(d[r]);
+                else { x[8 * k + 2 * r] = feat_widen_bits<FT>(d[r] & 0xFFFFu); x[8 * k + 2 * r + 1] = feat_widen_bits<FT>(d[r] >> 16); }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 32; ++j) v[j] = 0.0f;
+        __syncthreads();                          // (every word has left the tile before the first plane word lands on it)
+    } else if (cg * 32 + 32 <= C) {
         // all 32 channels of the word exist (wave-uniform: a wave is one channel word): 32 plain loads off ONE address - the per-channel
         // predicate cost 14 instructions per load, as many as the encoder steps themselves (round 5: the launch was VALU-bound at 62 % of
         // the HBM rate).  Lanes past the level's last position read its last position; their words are never stored
@@ -185,6 +220,24 @@ __global__ __launch_bounds__(256) void k_encode_levels_h(const EncLevels lv, int
     const int local = blockIdx.x - lv.blk_base[l];
     encode_block<EM>(reinterpret_cast<const FT*>(lv.feat[l]), C, lv.HW[l], Cw, T, p, eth, planes + (size_t)lv.pos_base[l] * (wm_rows ? 1 : Cw),
                      plane_stride, local / lv.bpi[l], local % lv.bpi[l], blockIdx.y, lv.Wpad[l], wm_rows, cmp ? cmp + lv.pos_base[l] : nullptr, nd);
+}
+
+// channels-last forms of the two launches above (new symbols; fp32, fp16 and bf16 elements): same grids, dynamic LDS ENC_NHWC_LDS_BYTES
+template <int EM, typename FT>
+__global__ __launch_bounds__(256) void k_encode_nhwc(const float* __restrict__ feat, int C, int HW, int Cw,
+                                                     int T, NeuronP p, const EncTh eth, uint32_t* __restrict__ planes,
+                                                     size_t plane_stride) {
+    encode_block<EM, FT, true>(reinterpret_cast<const FT*>(feat), C, HW, Cw, T, p, eth, planes, plane_stride, blockIdx.z, blockIdx.x, blockIdx.y);
+}
+template <int EM, typename FT>
+__global__ __launch_bounds__(256) void k_encode_levels_nhwc(const EncLevels lv, int C, int Cw, int T, NeuronP p, const EncTh eth,
+                                                            uint32_t* __restrict__ planes, size_t plane_stride, size_t wm_rows,
+                                                            uint32_t* __restrict__ cmp, int nd) {
+    int l = 0;
+    while (l + 1 < lv.n_levels && (int)blockIdx.x >= lv.blk_base[l + 1]) ++l;
+    const int local = blockIdx.x - lv.blk_base[l];
+    encode_block<EM, FT, true>(reinterpret_cast<const FT*>(lv.feat[l]), C, lv.HW[l], Cw, T, p, eth, planes + (size_t)lv.pos_base[l] * (wm_rows ? 1 : Cw),
+                               plane_stride, local / lv.bpi[l], local % lv.bpi[l], blockIdx.y, lv.Wpad[l], wm_rows, cmp ? cmp + lv.pos_base[l] : nullptr, nd);
 }
 
 // K1b: encoder on row-major x[R][D] -> bit-planes [T][R][Dw]; a wave covers 64 consecutive reduction indices per
@@ -985,3 +1038,138 @@ __device__ __forceinline__ void roi_align_encode_perm_block(const RoiArgs& a) {
 }
 template <int RW, typename FT>
 __global__ __launch_bounds__(256) void k_roi_align_encode_perm_h(const RoiArgs a) { roi_align_encode_perm_block<RW, FT>(a); }
+
+// K1f: K1e on channels-last maps [N][H][W][C] (SNN_FEAT_NHWC; fp32, fp16 and bf16 elements).  The lanes of a wave are the 64 CHANNELS of one
+// (RoI, bin): each of the bin's 16 taps is one contiguous run per load instruction (256 bytes fp32, 128 bytes half; a half element is one
+// 2-byte load - the width its address guarantees), and the ballot of a step IS the bin-major word pair (k' = bin * C + channel) - no 8 x 8 ballot
+// transposes, no second LDS buffer.  Work-groups, sample tables (the operations of roi_bilinear, op for op), the order of the four samples, the
+// clamped-column rule (pair base xe.a, clamped xe.b: x_low = a + b, x_high = a + 1) and the store phase are those of k_roi_align_encode_perm;
+// a.cmp == nullptr leaves every plane raw (windows beyond 12 planes: k_compress_planes follows, as after k_permute_planes).
+// THREE COPIES: the sample-table construction and the store phase below are also written out in k_roi_align_encode_perm and in
+// roi_align_encode_perm_block (the fp32 kernel keeps the parent's text verbatim so that its instruction stream does not move; a shared body
+// re-scheduled it) - a fix to the clamped-column rule, the table layout or the cmp layout belongs in all three.
+template <int RW, typename FT>
+__global__ __launch_bounds__(256) void k_roi_align_encode_nhwc(const RoiArgs a) {
+    constexpr int RG = 4 * RW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pbuf[];          // word pairs [t][7][RG] (8 bytes each)
+    __shared__ RoiTabEntry tab[4][RW][16];                                        // per wave and RoI: 0, 1 = the two sample rows of ph; 2 .. 15 = sample columns
+    __shared__ uint16_t code[256];
+    code[threadIdx.x] = sp_byte_code(threadIdx.x);
+    const int T = a.T;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // work-group -> (channel pair-block cp, RoI group, bin row), as in k_roi_align_encode_perm
+    const int n_cp = a.C / 64, n_items = a.n_rg * 7;
+    int cp, item;
+    if (8 % n_cp == 0) {
+        const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3, per = 8 / n_cp;
+        cp = xcd % n_cp;
+        item = jj * per + xcd / n_cp;
+    } else { cp = blockIdx.x % n_cp; item = blockIdx.x / n_cp; }
+    if (item >= n_items) return;
+    const int rgrp = item / 7, ph = item - 7 * rgrp;
+    const int r0 = rgrp * RG;
+    // ---- sample tables of this wave's RoIs (K1c'': same operations, same order)
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int r = r0 + wave * RW + i;                        // wave-uniform
+        if (r >= a.R) break;
+        const RoiLevel L = a.lv[a.roi_level[r]];
+        const float* roi = a.rois + (size_t)r * 4;
+        if (lane < 16) {
+            // lane 0, 1: sample row s = 2 ph + lane;  lane 2 .. 15: sample column s = lane - 2 = 2 pw + ix
+            const bool is_x = lane >= 2;
+            const int sidx = is_x ? lane - 2 : 2 * ph + lane, pb = sidx >> 1, ii = sidx & 1;
+            const float lo = __fmul_rn(is_x ? roi[0] : roi[1], L.scale);
+            const float ext = fmaxf(__fsub_rn(__fmul_rn(is_x ? roi[2] : roi[3], L.scale), lo), 1.0f);
+            const float bin = __fdiv_rn(ext, 7.0f);
+            const float b0 = __fadd_rn(lo, __fmul_rn((float)pb, bin));
+            float y = __fadd_rn(b0, __fdiv_rn(__fmul_rn((float)ii + 0.5f, bin), 2.0f));
+            const int n = is_x ? L.W : L.H;
+            RoiTabEntry e;
+            if (y < -1.0f || y > (float)n) { e.a = 0; e.b = 0; e.l = -1.0f; e.h = 0.0f; }     // outside the map: l < 0, offsets stay valid
+            else {
+                y = fmaxf(y, 0.0f);
+                int y_low = (int)y, y_high;
+                if (y_low >= n - 1) { y_high = y_low = n - 1; y = (float)y_low; } else y_high = y_low + 1;
+                e.l = __fsub_rn(y, (float)y_low);
+                e.h = __fsub_rn(1.0f, e.l);
+                if (is_x) { e.b = y_high == y_low; e.a = e.b ? y_low - 1 : y_low; }      // pair base, clamped
+                else { e.a = y_low * L.W; e.b = y_high * L.W; }
+            }
+            tab[wave][i][lane] = e;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const unsigned C = (unsigned)a.C, c = (unsigned)(cp * 64 + lane);
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const int rl = wave * RW + i, r = r0 + rl;               // wave-uniform
+        if (r >= a.R) break;
+        const RoiLevel L = a.lv[a.roi_level[r]];
+        const FT* const f = reinterpret_cast<const FT*>(L.feat) + (size_t)a.roi_batch[r] * a.C * (size_t)(L.H * L.W) + c;
+        const RoiTabEntry* const tb = tab[wave][i];
+        RoiTabEntry ye[2];
+        ye[0] = tb[0]; ye[1] = tb[1];
+#pragma unroll 1
+        for (int pw = 0; pw < 7; ++pw) {
+            RoiTabEntry xe[2];
+            xe[0] = tb[2 + 2 * pw]; xe[1] = tb[3 + 2 * pw];
+            // all sixteen taps are requested before any is used (samples outside the map read row / columns 0, 1 and are dropped)
+            float tp[2][2][4];
+#pragma unroll
+            for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                for (int ix = 0; ix < 2; ++ix) {
+                    const unsigned xl = (unsigned)(xe[ix].a + xe[ix].b), xh = (unsigned)(xe[ix].a + 1);
+                    tp[iy][ix][0] = feat_widen(f[((unsigned)ye[iy].a + xl) * C]);
+                    tp[iy][ix][1] = feat_widen(f[((unsigned)ye[iy].a + xh) * C]);
+                    tp[iy][ix][2] = feat_widen(f[((unsigned)ye[iy].b + xl) * C]);
+                    tp[iy][ix][3] = feat_widen(f[((unsigned)ye[iy].b + xh) * C]);
+                }
+            float sm[2][2];
+#pragma unroll
+            for (int iy = 0; iy < 2; ++iy)
+#pragma unroll
+                for (int ix = 0; ix < 2; ++ix) {
+                    const bool ok = ye[iy].l >= 0.0f && xe[ix].l >= 0.0f;
+                    const float v1 = tp[iy][ix][0], v2 = tp[iy][ix][1], v3 = tp[iy][ix][2], v4 = tp[iy][ix][3];
+                    float acc = __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].h), v1);
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].h, xe[ix].l), v2));
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].h), v3));
+                    acc = __fadd_rn(acc, __fmul_rn(__fmul_rn(ye[iy].l, xe[ix].l), v4));
+                    sm[iy][ix] = ok ? acc : 0.0f;
+                }
+            const float val = __fdiv_rn(__fadd_rn(__fadd_rn(__fadd_rn(sm[0][0], sm[0][1]), sm[1][0]), sm[1][1]), 4.0f);
+            unsigned long long prev = 0ull;
+            unsigned long long* const dst = reinterpret_cast<unsigned long long*>(pbuf) + (size_t)pw * RG + rl;
+            for (int t = 0; t < T; ++t) {
+                const unsigned long long cum = __ballot(val >= a.eth.th[t]);                   // first spike at or before t
+                const unsigned long long m = cum & ~prev;                                      // bit = channel 64 cp + lane: the word pair of the bin
+                prev = cum;
+                if (lane == 0) dst[(size_t)t * (7 * RG)] = m;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- store: item = (t, pw, RoI): the word pair (channel blocks 2 cp, 2 cp + 1) of bin ph * 7 + pw
+    const int cbn = a.C / 32;
+    const size_t R = (size_t)a.R, cmp_plane = (size_t)(a.Dw / 2) * SP_A_ARR * R;
+    for (int idx = threadIdx.x; idx < T * 7 * RG; idx += 256) {
+        const int rl = idx % RG, pwi = (idx / RG) % 7, t = idx / (7 * RG);
+        const size_t row = (size_t)(r0 + rl);
+        if (row >= R) continue;
+        const uint2 w2 = *reinterpret_cast<const uint2*>(pbuf + (size_t)idx * 8);
+        const int bin = ph * 7 + pwi;
+        if (t < a.nd || !a.cmp) {
+            uint32_t* o = a.planes + (size_t)t * a.plane_stride + (size_t)(bin * cbn + 2 * cp) * R + row;
+            o[0] = w2.x; o[R] = w2.y;
+        } else {
+            uint32_t c4[4];
+            sp_compress_pair(w2.x, w2.y, code, c4);
+            uint32_t* o = a.cmp + (size_t)(t - a.nd) * cmp_plane + (size_t)(bin * (cbn / 2) + cp) * SP_A_ARR * R + row;
+#pragma unroll
+            for (int j = 0; j < SP_A_ARR; ++j) o[(size_t)j * R] = c4[j];
+        }
+    }
+}

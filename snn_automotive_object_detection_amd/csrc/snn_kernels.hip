@@ -509,17 +509,28 @@ __global__ __launch_bounds__(1024) void k_det_payload(const float* __restrict__ 
     if (tid == 0) counts[img] = n;
 }
 
-// ---- the encoder kernel of a launch: K<..> for fp32 features, K_h<.., feat_f16 | feat_bf16> for half-precision ones (fdt has passed check_feat)
-#define ENC_PICKER(fn, K)                                                                                                                                  \
+// ---- the encoder kernel of a launch: K<..> for fp32 features, K_h<.., feat_f16 | feat_bf16> for half-precision ones (fdt has passed check_feat);
+// with the layout bit SNN_FEAT_NHWC the channels-last kernel KN<.., float | feat_f16 | feat_bf16> (nullptr: the launch has none)
+#define ENC_PICKER(fn, K, KN)                                                                                                                              \
     template <int EM>                                                                                                                                      \
     static const void* fn##_of(int fdt) {                                                                                                                  \
+        if (fdt & SNN_FEAT_NHWC) return KN<EM>(fdt & ~SNN_FEAT_NHWC);                                                                                      \
         return fdt == SNN_FEAT_F16 ? (const void*)K##_h<EM, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)K##_h<EM, feat_bf16> : (const void*)K<EM>;      \
     }                                                                                                                                                      \
     static const void* fn(int em, int fdt) { return em == ENC_QUANT ? fn##_of<ENC_QUANT>(fdt) : em == ENC_ZR ? fn##_of<ENC_ZR>(fdt) : fn##_of<ENC_GENERIC>(fdt); }
-ENC_PICKER(encode_nchw_kernel, k_encode_nchw)
-ENC_PICKER(encode_levels_kernel, k_encode_levels)
-ENC_PICKER(encode_rows_wm_kernel, k_encode_rows_wm)
+template <int EM> static const void* enc_nhwc_stage(int dt) {
+    return dt == SNN_FEAT_F16 ? (const void*)k_encode_nhwc<EM, feat_f16> : dt == SNN_FEAT_BF16 ? (const void*)k_encode_nhwc<EM, feat_bf16> : (const void*)k_encode_nhwc<EM, float>;
+}
+template <int EM> static const void* enc_nhwc_levels(int dt) {
+    return dt == SNN_FEAT_F16 ? (const void*)k_encode_levels_nhwc<EM, feat_f16> : dt == SNN_FEAT_BF16 ? (const void*)k_encode_levels_nhwc<EM, feat_bf16>
+                                                                                                       : (const void*)k_encode_levels_nhwc<EM, float>;
+}
+template <int EM> static const void* enc_nhwc_none(int) { return nullptr; }      // (the row-fed entries refuse the bit)
+ENC_PICKER(encode_nchw_kernel, k_encode_nchw, enc_nhwc_stage)
+ENC_PICKER(encode_levels_kernel, k_encode_levels, enc_nhwc_levels)
+ENC_PICKER(encode_rows_wm_kernel, k_encode_rows_wm, enc_nhwc_none)
 #undef ENC_PICKER
+static size_t feat_elem_bytes(int fdt) { return (fdt & ~SNN_FEAT_NHWC) == SNN_FEAT_F32 ? 4 : 2; }
 template <int RB, int NW>
 static const void* encode_rows_perm_of(int fdt) {
     return fdt == SNN_FEAT_F16 ? (const void*)k_encode_rows_perm_h<49, RB, NW, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)k_encode_rows_perm_h<49, RB, NW, feat_bf16>
@@ -534,6 +545,11 @@ static const void* roi_align_encode_tab_kernel(int fdt) {
 }
 template <int RW>
 static const void* roi_align_encode_perm_kernel(int fdt) {
+    if (fdt & SNN_FEAT_NHWC) {                                     // (channels-last maps: lanes = channels, snn_encode.h K1f)
+        const int dt = fdt & ~SNN_FEAT_NHWC;
+        return dt == SNN_FEAT_F16 ? (const void*)k_roi_align_encode_nhwc<RW, feat_f16> : dt == SNN_FEAT_BF16 ? (const void*)k_roi_align_encode_nhwc<RW, feat_bf16>
+                                                                                                              : (const void*)k_roi_align_encode_nhwc<RW, float>;
+    }
     return fdt == SNN_FEAT_F16 ? (const void*)k_roi_align_encode_perm_h<RW, feat_f16> : fdt == SNN_FEAT_BF16 ? (const void*)k_roi_align_encode_perm_h<RW, feat_bf16>
                                                                                                               : (const void*)k_roi_align_encode_perm<RW>;
 }
@@ -1399,11 +1415,20 @@ static int check_T(int T, const char* who) {
     return 0;
 }
 
-// half-precision features (include/snn_hip.h): a known dtype, and a 16-byte aligned base pointer for the 16-bit types
+// typed features (include/snn_hip.h): a known dtype (with or without the layout bit SNN_FEAT_NHWC), and a 16-byte aligned base pointer for
+// the 16-bit types and for every channels-last map
 static int check_feat(const void* ptr, int fdt, const char* who) {
-    if (fdt != SNN_FEAT_F32 && fdt != SNN_FEAT_F16 && fdt != SNN_FEAT_BF16) return fail(-1, "%s: unknown feat_dtype %d", who, fdt);
-    if (fdt != SNN_FEAT_F32 && ptr && ((uintptr_t)ptr & 15)) return fail(-1, "%s: half-precision features must be 16-byte aligned", who);
+    const int dt = fdt & ~SNN_FEAT_NHWC;
+    if (dt != SNN_FEAT_F32 && dt != SNN_FEAT_F16 && dt != SNN_FEAT_BF16) return fail(-1, "%s: unknown feat_dtype %d", who, fdt);
+    if ((fdt & SNN_FEAT_NHWC) && ptr && ((uintptr_t)ptr & 15)) return fail(-1, "%s: channels-last features must be 16-byte aligned", who);
+    if (dt != SNN_FEAT_F32 && ptr && ((uintptr_t)ptr & 15)) return fail(-1, "%s: half-precision features must be 16-byte aligned", who);
     return 0;
+}
+// the row-fed entries: pooled rows have no layout
+static int check_feat_rows(const void* ptr, int fdt, const char* who) {
+    if (check_feat(nullptr, fdt, who)) return -1;
+    if (fdt & SNN_FEAT_NHWC) return fail(-1, "%s: SNN_FEAT_NHWC on a row-fed entry (pooled rows have no layout)", who);
+    return check_feat(ptr, fdt, who);
 }
 
 int snn_encode_nchw(const float* feat, int N, int C, int H, int W, int T, const snn_params* p,
@@ -1418,13 +1443,16 @@ int snn_encode_nchw_typed(const void* feat_v, int fdt, int N, int C, int H, int 
         return fail(-1, "snn_encode_nchw: bad argument");
     if (check_T(T, "snn_encode_nchw")) return -1;
     if (check_feat(feat_v, fdt, "snn_encode_nchw")) return -1;
+    const bool nhwc = (fdt & SNN_FEAT_NHWC) != 0;
+    if (nhwc && C % 32) return SNN_STATUS_NO_TYPED_KERNEL;       // (channels-last kernels: whole channel words only; nothing enqueued)
     const int Cw = cdiv(C, 32), HW = H * W;
     NeuronP np = make_p(p, p->v_th_enc);
     if (knobs().stage_periods && enc_zero_rest(np)) np.v_fire = ENC_FIRED;      // (tests / tools: period planes)
     const EncTh* eth;
     const int em = enc_mode(np, &eth);
     const dim3 g(cdiv(HW, ENC_PB), cdiv(Cw, ENC_WB), N);
-    launch_picked(encode_nchw_kernel(em, fdt), g, dim3(256), ENC_LDS_BYTES(T), (hipStream_t)s, feat, C, HW, Cw, T, np, *eth, planes, plane_stride);
+    launch_picked(encode_nchw_kernel(em, fdt), g, dim3(256), nhwc ? ENC_NHWC_LDS_BYTES(T, feat_elem_bytes(fdt)) : ENC_LDS_BYTES(T), (hipStream_t)s, feat, C,
+                  HW, Cw, T, np, *eth, planes, plane_stride);
     SNN_CHECK_LAUNCH("k_encode_nchw");
     return 0;
 }
@@ -1577,6 +1605,8 @@ int snn_roi_align_encode(const snn_roi_level* levels_host, int n_levels, int C, 
 int snn_roi_align_encode_typed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois, const int* roi_batch,
                                const int* roi_level, int R, int T, const snn_params* p, uint32_t* planes,
                                size_t plane_stride, float* pooled_dbg, snn_stream_t s) {
+    if (fdt & SNN_FEAT_NHWC)                                    // (flatten-order planes are not built for channels-last maps; nothing enqueued)
+        return check_feat(nullptr, fdt, "snn_roi_align_encode") ? -1 : SNN_STATUS_NO_TYPED_KERNEL;
     // (SNN_STAGE_PLANES=wm, tests / tools: the planes come back word-major [T][Dw][R] - the layout and the kernels the fused head uses)
     return roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, T, p, planes, plane_stride, pooled_dbg,
                                  knobs().stage_wm, s, knobs().stage_periods && p && p->v_leak == 0.0f && p->v_reset == 0.0f, fdt);
@@ -1959,6 +1989,8 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
             return fail(-1, "snn_rpn_head_forward: bad level %d", l);
     for (int l = 0; l < n_levels; ++l)
         if (check_feat(lv[l].feat, fdt, "snn_rpn_head_forward")) return -1;
+    const bool nhwc = (fdt & SNN_FEAT_NHWC) != 0;
+    if (nhwc && C % 32) return SNN_STATUS_NO_TYPED_KERNEL;       // (channels-last kernels: whole channel words only; nothing enqueued)
     int max_n = 0;
     const long long P = rpn_positions(lv, n_levels, &max_n);
     size_t o_spk, o_cur, o_cnt, need;
@@ -2023,7 +2055,8 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         const int em = enc_mode(np, &eth);
         const dim3 ge(blocks, cdiv(Cw, ENC_WB));
         uint32_t* const cmp_e = em == ENC_QUANT ? enc_cmp : nullptr;         // (the compressed-plane fold: period planes by thresholds only)
-        launch_picked(encode_levels_kernel(em, fdt), ge, dim3(256), ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np, *eth, enc, enc_stride, wm_rows, cmp_e, em == ENC_QUANT ? 2 : 0);
+        launch_picked(encode_levels_kernel(em, fdt), ge, dim3(256), nhwc ? ENC_NHWC_LDS_BYTES(Tc, feat_elem_bytes(fdt)) : ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np,
+                      *eth, enc, enc_stride, wm_rows, cmp_e, em == ENC_QUANT ? 2 : 0);
         SNN_CHECK_LAUNCH("k_encode_levels");
     }
     if (stage_mask & SNN_STAGE_CONV_LIF) {
@@ -2473,6 +2506,7 @@ struct DetPlan {
     size_t o_raw;                        // where the unfolded encoder writes: o_enc, or the last region for permuted fc6 weights (det_ws_perm_offset)
     DetWindows win;
     bool wm, per;                        // encoder planes word-major (det_planes_wm); fc6 on the encoder's period planes (snn_common.h)
+    bool bin_major;                      // an unfolded encoder already wrote RAW planes in fc6's bin-major order at o_enc (channels-last RoIAlign): no k_permute_planes
 };
 static int det_plan(const char* who, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, bool spike_rates, bool wm_ok,
                     size_t ws_bytes, DetPlan* dp) {
@@ -2481,6 +2515,7 @@ static int det_plan(const char* who, int R, int D, int Hd, int T, int w6_inner, 
     if (ws_bytes < need) return fail(-2, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
     if (check_T(T, who)) return -1;
     dp->o_raw = w6_inner > 1 ? det_ws_perm_offset(R, D, Hd, T) : dp->o_enc;
+    dp->bin_major = false;
     dp->win = det_windows(p, T, spike_rates);
     dp->wm = det_planes_wm(p, dp->win) && wm_ok;
     dp->per = knobs().periods && periods_possible(p) && det_b3_tiles(p, dp->win);
@@ -2538,7 +2573,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
     const int Hw = cdiv(Hd, 32), Hp = Hw * 32;
     g_last_det_planes[0] = o_s6; g_last_det_planes[1] = o_s7; g_last_det_planes[2] = enc_wm ? 1 : 0;
     int rc;
-    if (k_inner > 1 && !folded) {
+    if (k_inner > 1 && !folded && !dp.bin_major) {
         // fc6's weights were packed in the permuted reduction order k' = s * C + c (snn_pack_linear_weight_bf16x3_perm): bring the
         // encoder's planes into the same order (snn_sparse.h: k_permute_planes).  Word-major planes of the fused bf16x3 layers only.
         const int C = D / k_inner;
@@ -2610,7 +2645,7 @@ static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, i
         return fail(-1, "snn_det_head_forward: null argument");
     if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward: bad shape");
     if (check_T(T, "snn_det_head_forward")) return -1;          // (the row-fed entry points check T before the workspace)
-    if (check_feat(x, fdt, "snn_det_head_forward")) return -1;
+    if (check_feat_rows(x, fdt, "snn_det_head_forward")) return -1;
     DetPlan dp;
     int rc;
     if ((rc = det_plan("snn_det_head_forward", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, encode_rows_wm_ok(x, D), ws_bytes, &dp)))
@@ -2658,19 +2693,36 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
     int rc;
     if ((rc = det_plan("snn_det_head_forward_roialign", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, true, ws_bytes, &dp))) return rc;
     if (w6_inner > 1 && (!dp.wm || w6_inner != 49)) return fail(-4, "snn_det_head_forward_roialign: permuted fc6 weights need inner = 49 and the word-major fused bf16x3 path");
+    // the feature dtype / layout code and every level's base pointer, once, before anything is asked of fc6 or enqueued
+    if (check_feat(nullptr, fdt, "snn_det_head_forward_roialign")) return -1;
+    for (int l = 0; levels_host && n_levels <= 4 && l < n_levels; ++l)
+        if (check_feat(levels_host[l].feat, fdt, "snn_det_head_forward_roialign")) return -1;
     // round 6: the RoIAlign encoder folds as the row encoder does since round 5 (k_roi_align_encode_perm).
     // Planned for windows of up to 12 planes (T_det <= 14): measured on the bench's pyramid, 2000 RoIs (profiles/r6_roi_fold_ab.txt, same lease) the fused
     // head takes 0.943 against 0.948 ms at T_det = 12 - the launch itself is 30 us slower than the table kernel (7 of 8 lanes per bin row, a second
     // pass that transposes the ballots) and saves k_permute_planes + k_compress_planes (38 us) and their two 31-MB plane copies - but 2.04 against
     // 1.88 ms at T_det = 24, where its 44 KB of LDS leave three work-groups per CU to a launch that lives on loads in flight.
-    bool feed_ok = knobs().roi_tab && dp.win.enc_steps <= 12 && C % 64 == 0 && levels_host && rois && roi_batch && roi_level && n_levels > 0 &&
-                   n_levels <= 4;
-    for (int l = 0; l < n_levels && feed_ok; ++l)
-        feed_ok = levels_host[l].feat && levels_host[l].H > 0 && levels_host[l].W >= 2 && (long long)C * levels_host[l].H * levels_host[l].W < (1ll << 29);
+    bool feed_geo = knobs().roi_tab && C % 64 == 0 && levels_host && rois && roi_batch && roi_level && n_levels > 0 && n_levels <= 4;
+    for (int l = 0; l < n_levels && feed_geo; ++l)
+        feed_geo = levels_host[l].feat && levels_host[l].H > 0 && levels_host[l].W >= 2 && (long long)C * levels_host[l].H * levels_host[l].W < (1ll << 29);
+    const bool feed_ok = feed_geo && dp.win.enc_steps <= 12;
     NeuronP np;
     const EncTh* eth_f = nullptr;
     const bool fold = det_fc6_folds(feed_ok, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
-    if (fold) {
+    // channels-last maps (SNN_FEAT_NHWC): one kernel, for the plans in which fc6 reads bin-major period planes - folded as above, or (longer windows,
+    // a dense fc6) every plane raw in bin-major order where k_permute_planes would have put it, k_compress_planes following as before
+    const bool nhwc = (fdt & SNN_FEAT_NHWC) != 0;
+    bool nhwc_raw = false;
+    if (nhwc && !fold) {
+        nhwc_raw = feed_geo && w6_inner == 49 && dp.wm && dp.per;
+        if (nhwc_raw) {
+            np = make_p(p, p->v_th_enc);
+            np.v_fire = ENC_FIRED;
+            nhwc_raw = enc_zero_rest(np) && enc_mode(np, &eth_f) == ENC_QUANT;
+        }
+        if (!nhwc_raw) return SNN_STATUS_NO_TYPED_KERNEL;       // (nothing has been enqueued)
+    }
+    if (fold || nhwc_raw) {
         constexpr int RW = 4;
         RoiArgs fa;
         memset(&fa, 0, sizeof(fa));
@@ -2679,16 +2731,15 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
         }
         fa.p = np; fa.quant = 1; fa.eth = *eth_f;
         fa.rois = rois; fa.roi_batch = roi_batch; fa.roi_level = roi_level;
-        fa.planes = (uint32_t*)((char*)ws + dp.o_enc); fa.cmp = (uint32_t*)((char*)ws + dp.o_cur); fa.nd = 2;
+        fa.planes = (uint32_t*)((char*)ws + dp.o_enc); fa.cmp = fold ? (uint32_t*)((char*)ws + dp.o_cur) : nullptr; fa.nd = 2;
         fa.plane_stride = (unsigned long long)R * cdiv(D, 32); fa.R = R; fa.C = C; fa.T = dp.win.enc_steps; fa.Dw = cdiv(D, 32);
         fa.RW = RW; fa.n_rg = cdiv(R, 4 * RW);
         const int n_cp = C / 64, n_items = fa.n_rg * 7;
         const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
-        const size_t lds = (size_t)fa.T * (7 + 8) * 4 * RW * 8;                  // word pairs + raw ballots
-        for (int l = 0; l < n_levels; ++l)
-            if (check_feat(levels_host[l].feat, fdt, "snn_det_head_forward_roialign")) return -1;
+        const size_t lds = (size_t)fa.T * (nhwc ? 7 : 7 + 8) * 4 * RW * 8;       // word pairs + raw ballots (channels-last: word pairs only)
         launch_picked(roi_align_encode_perm_kernel<RW>(fdt), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
         SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
+        dp.bin_major = nhwc_raw;
     } else if ((rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, dp.win.enc_steps, p,
                                            (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per, fdt))) {
         return rc;                                              // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)

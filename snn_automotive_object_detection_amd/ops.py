@@ -62,41 +62,73 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 # Half-precision features (include/snn_hip.h, SNN_FEAT_*): fp16 / bf16 CUDA tensors go to the typed entry points uncast - an element means its
 # exact fp32 value, the encoder kernels widen it in registers, outputs stay fp32.  Every other dtype is widened to fp32 as before.
 _HALF = {torch.float16: _lib.FEAT_DTYPES["f16"], torch.bfloat16: _lib.FEAT_DTYPES["bf16"]}
-# call record of the typed path: "f16" / "bf16" = typed calls that ran, "no_typed_kernel" = calls whose launch plan has no typed encoder
-# (the typed entry enqueued nothing; the features were widened and the fp32 entry ran)
-feature_calls = {"f16": 0, "bf16": 0, "no_typed_kernel": 0}
+# Channels-last (NHWC) maps (SNN_FEAT_NHWC): a CUDA tensor that is dense in torch.channels_last (and not in the default format) goes to the typed
+# entry points as it is, with the layout bit - no transposing copy in front of the first kernel.  Values never depend on the layout.
+_NHWC_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+# call record of the typed path: "f16" / "bf16" = typed calls that ran, "nhwc" = calls that ran on channels-last maps, "no_typed_kernel" = calls
+# whose launch plan has no kernel for the dtype / layout (the typed entry enqueued nothing; channels-last maps were converted to NCHW, half
+# features without an NCHW typed kernel widened, and the call ran again)
+feature_calls = {"f16": 0, "bf16": 0, "no_typed_kernel": 0, "nhwc": 0}
 
 
 def _feat(t: torch.Tensor) -> torch.Tensor:
-    """a feature tensor as the kernels take it: half-precision CUDA tensors contiguous and 16-byte aligned, else fp32 contiguous"""
+    """a feature tensor as the NCHW kernels take it: half-precision CUDA tensors contiguous and 16-byte aligned, else fp32 contiguous"""
     if t.is_cuda and t.dtype in _HALF:
         t = t.detach().contiguous()
         return t.clone() if t.data_ptr() % 16 else t
     return _f32c(t)
 
 
+def feat_layout(t: torch.Tensor) -> Optional[str]:
+    """the dense layout of a feature map [N, C, H, W], from sizes and strides alone (no device needed): "nchw" (default format), "nhwc"
+    (torch.channels_last), "either" (the same bytes in both: H W == 1 or C == 1), or None (neither - a sliced view, say)"""
+    nchw = t.is_contiguous()
+    nhwc = t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+    return "either" if nchw and nhwc else "nchw" if nchw else "nhwc" if nhwc else None
+
+
+def levels_nhwc(feats) -> bool:
+    """do the levels of one call take the channels-last path?  They share a layout: at least one is dense in channels_last only, every other one
+    is that or "either", and the dtypes are ones the kernels read (else all of them go through the NCHW conversion, without an error)"""
+    lay = [feat_layout(f) for f in feats]
+    return "nhwc" in lay and all(l in ("nhwc", "either") for l in lay) and all(f.dtype in _NHWC_DTYPES for f in feats)
+
+
 def _feat_levels(feats, what: str):
-    """-> (the levels as the kernels take them, their common SNN_FEAT_* code); levels of one call share a dtype"""
+    """-> (the levels as the kernels take them, their common SNN_FEAT_* code, with the layout bit for channels-last levels); levels of one
+    call share a dtype"""
     feats = list(feats)
     for f in feats:
         _need_gpu(f, what)
     if any(f.dtype in _HALF for f in feats) and len({f.dtype for f in feats}) > 1:
         raise _lib.SnnHipError("%s: the levels of one call must share a dtype, got %s" % (what, sorted({str(f.dtype) for f in feats})))
+    if levels_nhwc(feats):
+        feats = [f.detach() for f in feats]
+        feats = [f.clone(memory_format=torch.preserve_format) if f.data_ptr() % 16 else f for f in feats]
+        return feats, _HALF.get(feats[0].dtype, 0) | _lib.FEAT_NHWC
     feats = [_feat(f) for f in feats]
     return feats, (_HALF.get(feats[0].dtype, 0) if feats else 0)
 
 
 def _typed_call(call, feats, fdt: int, what: str) -> None:
-    """call(feats, fdt) -> status.  Half features whose launch plan has no typed encoder kernel (SNN_STATUS_NO_TYPED_KERNEL: nothing was
-    enqueued) are widened and go through the fp32 entry, as every feature did before"""
+    """call(feats, fdt) -> status.  Features whose launch plan has no kernel for them (SNN_STATUS_NO_TYPED_KERNEL: nothing was enqueued) take
+    the next plainer form and the call runs again: channels-last maps are converted to NCHW (half features keep their dtype), half NCHW
+    features are widened and go through the fp32 entry, as every feature did before"""
     rc = call(feats, fdt)
     if fdt and rc == _lib.NO_TYPED_KERNEL:
         feature_calls["no_typed_kernel"] += 1
-        feats, fdt = [_f32c(f) for f in feats], 0
-        rc = call(feats, fdt)
+        if fdt & _lib.FEAT_NHWC:
+            feats, fdt = [_feat(f) for f in feats], fdt & ~_lib.FEAT_NHWC
+            rc = call(feats, fdt)
+        if fdt and rc == _lib.NO_TYPED_KERNEL:
+            feats, fdt = [_f32c(f) for f in feats], 0
+            rc = call(feats, fdt)
     _lib.check(rc, what)
-    if fdt:
-        feature_calls["f16" if fdt == 1 else "bf16"] += 1
+    if fdt & _lib.FEAT_NHWC:
+        feature_calls["nhwc"] += 1
+    dt = fdt & ~_lib.FEAT_NHWC
+    if dt:
+        feature_calls["f16" if dt == _lib.FEAT_DTYPES["f16"] else "bf16"] += 1
 
 
 def _stream() -> int:
