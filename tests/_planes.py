@@ -47,7 +47,7 @@ def det_planes(dev, T, Hd, R):
     from snn_automotive_object_detection_amd import _lib, ops
     off3 = (C.c_uint64 * 3)()
     _lib.load().snn_debug_last_det_planes(off3)
-    n = T * (Hd // 32) * R * 4
+    n = T * ((Hd + 31) // 32) * R * 4
     ws = ops._WS.get(dev, 1)
     return ws[int(off3[0]): int(off3[0]) + n].clone(), ws[int(off3[1]): int(off3[1]) + n].clone(), int(off3[2])
 
@@ -65,7 +65,8 @@ def head_rpn_planes(dev, T, C_):
 def head_det_planes(dev, T, Hd, R):
     """lif6 / lif7 spike planes of the last detector forward as rows [T, R, Hd / 32]"""
     p6, p7, wm = det_planes(dev, T, Hd, R)
-    return rows_from_word_major(p6.view(torch.int32), T, R, Hd // 32, wm).contiguous(), p7.view(torch.int32).view(T, R, Hd // 32)
+    Hw = (Hd + 31) // 32
+    return rows_from_word_major(p6.view(torch.int32), T, R, Hw, wm).contiguous(), p7.view(torch.int32).view(T, R, Hw)
 
 
 # ---- what a readout is, from the planes --------------------------------------------------------------------------------------------------

@@ -1,0 +1,371 @@
+"""Dyadic weight grids (tests/_exact_grid.py) on the GPU: the zero-tolerance gate for addressing and accumulation.
+
+On these weights every partial sum of every dense contraction of the hot path - the 3x3 conv over 9 C spike inputs, fc6 over 49 C, fc7
+over Hd, in any order, over k-blocks, taps, period planes, k-splits and the secondary sparse pass - is an integer number of units below
+2^24 and therefore exact in fp32: the GPU's currents and the oracle's are the SAME number (tests/test_exact_grid_cpu.py proves the
+oracle's side against fp64).  So here
+
+  * stage level: currents are compared with torch.equal against the oracle's trace;
+  * head level: the hidden spike planes the modules left in their workspace equal the oracle's spk / spk6 / spk7 bit for bit, the
+    spike-rate mode's integer counts equal the oracle's, and the outputs are within CUR_TOL of the fp64 LI recursion on those planes
+    and within 1e-4 of the oracle at EVERY position.
+A difference is a wrong term - a misaddressed tap, a dropped plane, a term from the wrong nibble - not a tie: there are none.  The default
+`-m gpu` run takes the values on either side of every switch; the in-between ones are marked `sweep`.  mxfp6: the pack definition that
+tests/test_gpu_mx.py restates carries both grids exactly (every weight of a 32-block within 28 bits of the block maximum:
+tests/test_exact_grid_cpu.py::test_mx_pack_definition_carries_the_grids), so its heads run here under the same demands."""
+import ctypes as Ct
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _exact_grid as G
+from tests._planes import CUR_TOL, head_det_planes, head_rpn_planes, li_constants, li_fp64
+from tests._util import dense_to_planes, nchw_to_rows, planes_to_dense
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+
+def _with_sweep(values, between):
+    """the issue's values in the default run, the ones in between marked `sweep`"""
+    return sorted(list(values) + [pytest.param(v, marks=pytest.mark.sweep) for v in between], key=lambda v: v if isinstance(v, int) else v.values[0])
+
+
+# ---- stage level -------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ops():
+    from snn_automotive_object_detection_amd import ops
+    return ops
+
+
+def _three_planes(single: torch.Tensor) -> torch.Tensor:
+    """the single bf16 plane of precision "bf16" as the operand of the three-plane stage entries: (plane, 0, 0)"""
+    return torch.cat([single.view(-1), torch.zeros(2 * single.numel(), dtype=single.dtype, device=single.device)])
+
+
+def _conv_bf16x3_ldo(ops, enc, shapes3, C, wp, ldo):
+    """ops.spike_conv3x3_bf16x3 with a row stride of `ldo` >= Np floats"""
+    from snn_automotive_object_detection_amd import _lib
+    from snn_automotive_object_detection_amd.ops import snn_rpn_level, _ptr, _stream
+    enc, P, Pp = ops._conv_planes(enc, shapes3)
+    T, _, Cw = enc.shape
+    lv = (snn_rpn_level * len(shapes3))(*[snn_rpn_level(None, n, h, w, 0) for n, h, w in shapes3])
+    cur = torch.full((T, P, ldo), 7.0, dtype=torch.float32, device=enc.device)
+    _lib.check(_lib.load().snn_spike_conv3x3_bf16x3(_ptr(enc), Pp * Cw, lv, len(shapes3), C, C, T, _ptr(wp), _ptr(cur), ldo, _stream()),
+               "snn_spike_conv3x3_bf16x3")
+    return cur
+
+
+def _gemm_ldo(ops, entry, a_rows, K, N, wp, ldo):
+    from snn_automotive_object_detection_amd import _lib
+    from snn_automotive_object_detection_amd.ops import _ptr, _stream
+    cur = torch.full((a_rows.shape[0], ldo), 7.0, dtype=torch.float32, device=a_rows.device)
+    _lib.check(getattr(_lib.load(), entry)(_ptr(a_rows), a_rows.shape[0], K, N, _ptr(wp), _ptr(cur), ldo, _stream()), entry)
+    return cur
+
+
+def _conv_stage(ops, dev, case):
+    C, T = case["C"], case["T"]
+    shapes3 = [(case["N"], h, w) for h, w in case["shapes"]]
+    enc = torch.cat([dense_to_planes(nchw_to_rows(tr["z"])) for tr in case["traces"]], dim=1).to(dev)      # the oracle's encoder planes
+    exp = torch.cat([torch.from_numpy(nchw_to_rows(tr["cur"])) for tr in case["traces"]], dim=1)
+    w = case["w_shared"].to(dev)
+    packs = [ops.pack_conv3x3_bf16x3(w)]
+    if case["grid"] == "narrow":
+        packs.append(_three_planes(ops.pack_conv3x3_bf16(w)))
+    Np = (C + 31) // 32 * 32
+    for wp in packs:
+        cur = ops.spike_conv3x3_bf16x3(enc, shapes3, C, C, wp).cpu()
+        assert torch.equal(cur[:, :, :C], exp), float((cur[:, :, :C] - exp).abs().max())
+        assert not cur[:, :, C:].any()
+        pad = _conv_bf16x3_ldo(ops, enc, shapes3, C, wp, Np + 32).cpu()
+        assert torch.equal(pad[:, :, :C], exp)
+    assert exp.abs().max() > 0
+
+
+@pytest.mark.parametrize("shapes", G.LEVEL_SHAPES, ids=lambda s: "x".join("%d_%d" % hw for hw in s))
+def test_conv_currents_equal_the_oracle_over_level_shapes(ops, gpu_device, shapes):
+    for N in (1, 3):
+        _conv_stage(ops, gpu_device, G.rpn_shape_case(shapes, N))
+
+
+@pytest.mark.parametrize("C", G.CONV_CHANNELS)
+def test_conv_currents_equal_the_oracle_over_channel_counts(ops, gpu_device, C):
+    _conv_stage(ops, gpu_device, G.rpn_t_case(C, 8))
+
+
+def test_conv_currents_equal_the_oracle_on_the_narrow_grid(ops, gpu_device):
+    _conv_stage(ops, gpu_device, G.rpn_t_case(64, 8, "narrow"))
+
+
+def _gemm_stage(ops, dev, z, w, exp, grid):
+    """z {0, 1} [M, K], w [N, K], exp [M, N] (the oracle's F.linear) through spike_gemm_bf16x3 and spike_gemm (f32), plain and padded ldo"""
+    M, K = z.shape
+    N = w.shape[0]
+    a = dense_to_planes(z.numpy()[None])[0].to(dev)
+    wd = w.to(dev)
+    Np = (N + 31) // 32 * 32
+    runs = [("snn_spike_gemm_bf16x3", ops.spike_gemm_bf16x3, ops.pack_linear_bf16x3(wd)), ("snn_spike_gemm", ops.spike_gemm, ops.pack_linear(wd))]
+    if grid == "narrow":
+        runs.append(("snn_spike_gemm_bf16x3", ops.spike_gemm_bf16x3, _three_planes(ops.pack_linear_bf16(wd))))
+    for entry, fn, wp in runs:
+        cur = fn(a, K, N, wp).cpu()
+        assert torch.equal(cur[:, :N], exp), (entry, float((cur[:, :N] - exp).abs().max()))
+        pad = _gemm_ldo(ops, entry, a, K, N, wp, Np + 32).cpu()
+        assert torch.equal(pad[:, :N], exp), entry
+
+
+@pytest.mark.parametrize("M,K,N", G.GEMM_SHAPES)
+@pytest.mark.parametrize("grid", ["wide", "narrow"])
+def test_gemm_currents_equal_the_oracle(ops, gpu_device, M, K, N, grid):
+    c = G.gemm_case(M, K, N, M + N, grid)
+    assert c["cur"].abs().max() > 0
+    _gemm_stage(ops, gpu_device, c["z"], c["w"], c["cur"], grid)
+
+
+@pytest.mark.parametrize("T,grid", [(12, "wide"), (8, "narrow")])
+def test_fc6_fc7_currents_equal_the_oracle_trace(ops, gpu_device, T, grid):
+    case = G.det_t_case(T, grid)
+    tr = case["trace"]
+    R = case["R"]
+    _gemm_stage(ops, gpu_device, tr["z"].reshape(T * R, -1), case["w6"], tr["cur6"].reshape(T * R, -1), grid)
+    _gemm_stage(ops, gpu_device, tr["spk6"].reshape(T * R, -1), case["w7"], tr["cur7"].reshape(T * R, -1), grid)
+
+
+# ---- head level --------------------------------------------------------------------------------------------------------------------------
+def _lib():
+    from snn_automotive_object_detection_amd import _lib
+    return _lib.load()
+
+
+def _features(x: torch.Tensor, dev, feat, nhwc=False):
+    x = x.to(dev)
+    if feat is not None:
+        x = x.to({"fp16": torch.float16, "bf16": torch.bfloat16}[feat])
+    return x.contiguous(memory_format=torch.channels_last) if nhwc else x
+
+
+def _heads_w(case, precision):
+    w = torch.cat([case["w_cls"].flatten(1), case["w_bbox"].flatten(1)])
+    return w.to(torch.bfloat16).float() if precision == "bf16" else w
+
+
+def run_rpn(case, dev, precision="bf16x3", sparse=None, nhwc=False):
+    """both modes of RPNHeadSNN on a case: planes == the oracle's, counts == the oracle's, outputs at every position"""
+    import snn_automotive_object_detection_amd as pkg
+    C, A, T, N = case["C"], case["A"], case["T"], case["N"]
+    m = pkg.RPNHeadSNN(C, A, T).to(dev)
+    m.precision, m.li_order = precision, case["li_order"]
+    m.load_state_dict({"shared_conv.weight": case["w_shared"], "conv_cls.weight": case["w_cls"], "conv_bbox.weight": case["w_bbox"]})
+    feats = [_features(f, dev, case["feat"], nhwc) for f in case["feats"]]
+    a, b = li_constants()
+    for rates in (False, True):
+        m.spike_rates = rates
+        out = m(feats)
+        assert m._resolve_precision() == precision
+        if sparse is not None:
+            assert _lib().snn_debug_last_conv_path() == int(sparse), "not the launch this test is about"
+        got = planes_to_dense(head_rpn_planes(dev, T, C), C)
+        diff = got != case["spk"]
+        assert not diff.any(), "hidden planes differ from the oracle's at (step, position, channel) %s ... (%d in all)" % (np.argwhere(diff)[:4].tolist(), int(diff.sum()))
+        if rates:
+            assert np.array_equal(m.last_spike_counts[:, :N].cpu().numpy(), case["counts"])
+        last, _ = li_fp64(case["spk"], _heads_w(case, precision), a, b, case["li_order"])
+        pos = 0
+        for l, (H, W) in enumerate(case["shapes"]):
+            o = torch.cat([out[0][l], out[1][l]], dim=1).permute(0, 2, 3, 1).reshape(N * H * W, 5 * A).double().cpu().numpy()
+            assert np.abs(o - last[T - 1, pos:pos + N * H * W]).max() <= CUR_TOL
+            e = torch.cat([case["logits"][l], case["bbox"][l]], dim=1).permute(0, 2, 3, 1).reshape(N * H * W, 5 * A).numpy()
+            assert np.abs(o - e).max() <= TOL
+            pos += N * H * W
+    return m
+
+
+def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False):
+    import snn_automotive_object_detection_amd as pkg
+    R, C, Hd, K, T = case["R"], case["C"], case["Hd"], case["K"], case["T"]
+    d = pkg.FastRCNNPredictorSNNFull(C * 49, Hd, K, T).to(dev)
+    d.precision, d.li_order = precision, case["li_order"]
+    d.load_state_dict({"fc6.weight": case["w6"], "fc7.weight": case["w7"], "cls_score.weight": case["w_cls"], "bbox_pred.weight": case["w_bbox"]})
+    x = _features(case["x"], dev, case["feat"], nhwc)
+    tr = case["trace"]
+    e6, e7 = tr["spk6"].numpy(), tr["spk7"].numpy()
+    a, b = li_constants()
+    for rates in (False, True):
+        d.spike_rates = rates
+        out = d(x)
+        assert d._resolve_precision() == precision
+        if fc6_sparse is not None:                                   # (a pair: plain forward, spike-rate mode)
+            want = fc6_sparse[int(rates)] if isinstance(fc6_sparse, tuple) else fc6_sparse
+            assert _lib().snn_debug_last_fc6_path() == int(want), "not the launch this test is about"
+        p6, p7 = head_det_planes(dev, T, Hd, R)
+        n6 = T if rates else T - 1                                   # (without the rates lif6's spikes of the last step are never read and not formed)
+        g6, g7 = planes_to_dense(p6, Hd), planes_to_dense(p7, Hd)
+        d6, d7 = g6[:n6] != e6[:n6], g7 != e7
+        assert not d6.any(), "lif6 planes differ at (step, RoI, unit) %s ... (%d in all)" % (np.argwhere(d6)[:4].tolist(), int(d6.sum()))
+        assert not d7.any(), "lif7 planes differ at (step, RoI, unit) %s ... (%d in all)" % (np.argwhere(d7)[:4].tolist(), int(d7.sum()))
+        if rates:
+            c6, c7 = [c.cpu().numpy().astype(np.int64) for c in d.last_spike_counts]
+            assert np.array_equal(c6, case["counts"][0]) and np.array_equal(c7, case["counts"][1])
+            continue                                                 # (in this mode the detector's forward returns ONLY the rate rows: no cls / bbox to compare)
+        o = torch.cat([out[0], out[1]], dim=1).double().cpu().numpy()
+        last, _ = li_fp64(e7, _heads_w(case, precision), a, b, case["li_order"])
+        assert np.abs(o - last[T - 1]).max() <= CUR_TOL
+        assert np.abs(o - torch.cat([case["cls"], case["bbox"]], dim=1).numpy()).max() <= TOL
+    return d
+
+
+# RPN: dead steps (T = 1, 2), the dense tile (4), the dense / sparse switches at 5 and 16, the encoder's fold switch, the general epilogue (17, 26)
+@pytest.mark.parametrize("C", [64, 256])
+@pytest.mark.parametrize("T", _with_sweep(G.RPN_T, (3, 6, 7, 9, 10, 11, 13, 14, 15, 20, 24, 32)))
+def test_rpn_head_every_T_class(gpu_device, C, T):
+    run_rpn(G.rpn_t_case(C, T), gpu_device, sparse=5 <= T <= 16)
+
+
+# the sparse pair runs where the channel count padded to 32 gives an even number of plane words and one, two or four 64-column blocks:
+# 100 (-> 128) and 512; 3 pads to one word, 192 and 320 have three and five column blocks (tests/_abi_badargs.py pins 192 as dense too)
+@pytest.mark.parametrize("C,sparse", [(3, False), (100, True), (192, False), (320, False), (512, True)])
+def test_rpn_head_channel_counts(gpu_device, C, sparse):
+    assert C in G.RPN_C_AT_T8
+    run_rpn(G.rpn_t_case(C, 8), gpu_device, sparse=sparse)
+
+
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("shapes", G.LEVEL_SHAPES, ids=lambda s: "x".join("%d_%d" % hw for hw in s))
+def test_rpn_head_level_shapes(gpu_device, shapes, N):
+    run_rpn(G.rpn_shape_case(shapes, N), gpu_device, sparse=True)
+
+
+@pytest.mark.parametrize("T", _with_sweep(G.DET_T, (4, 5, 7, 9, 10, 11, 13, 15, 18, 20, 26, 28)))
+def test_det_head_every_T_class(gpu_device, T):
+    # fc6 goes to the sparse launch once it forms four live steps: T - 2 of them, T - 1 in spike-rate mode (which counts lif6's last step too)
+    run_det(G.det_t_case(T), gpu_device, fc6_sparse=(T >= 6, T >= 5))
+
+
+@pytest.mark.parametrize("C", [32, 64])
+@pytest.mark.parametrize("R", G.DET_R)
+def test_det_head_row_remainders(gpu_device, R, C):
+    """C = 32: 49 C / 32 is odd - fc6 on the dense tile; C = 64: the structured-sparse (FAT) fc6 launch of the production widths"""
+    run_det(G.det_r_case(R, C), gpu_device, fc6_sparse=C == 64)
+
+
+@pytest.mark.parametrize("C,Hd", G.DET_C_HD)
+def test_det_head_widths(gpu_device, C, Hd):
+    run_det(G.det_width_case(C, Hd), gpu_device, fc6_sparse=C % 64 == 0)     # bin-major fc6 on the sparse instruction needs C % 32 == 0 and 49 C / 32 even
+
+
+def test_voltage_first(gpu_device):
+    run_rpn(G.rpn_t_case(64, 12, "wide", "voltage_first"), gpu_device, sparse=True)
+    run_det(G.det_t_case(12, "wide", "voltage_first"), gpu_device, fc6_sparse=True)
+
+
+# ---- precisions ----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision,grid", [("f32", "wide"), ("f32_strict", "wide"), ("bf16", "narrow"), ("bf16x3", "narrow")])
+@pytest.mark.parametrize("T", G.PRECISION_T_RPN)
+def test_rpn_head_precisions(gpu_device, precision, grid, T):
+    run_rpn(G.rpn_t_case(64, T, grid), gpu_device, precision)
+
+
+@pytest.mark.parametrize("precision,grid", [("f32", "wide"), ("f32_strict", "wide"), ("bf16", "narrow"), ("bf16x3", "narrow")])
+@pytest.mark.parametrize("T", G.PRECISION_T_DET)
+def test_det_head_precisions(gpu_device, precision, grid, T):
+    run_det(G.det_t_case(T, grid), gpu_device, precision)
+
+
+@pytest.mark.parametrize("grid", ["wide", "narrow"])
+def test_heads_at_mxfp6(gpu_device, grid):
+    """fp4 x fp6 digit planes: every digit term of a dyadic weight is a multiple of the unit as well, so the sums stay exact"""
+    run_rpn(G.rpn_t_case(256, 8, grid), gpu_device, "mxfp6")
+    run_det(G.det_mx_case(grid), gpu_device, "mxfp6")
+
+
+# ---- knobs: one sparse-eligible case per head; each asserts the launch that ran ----------------------------------------------------------------
+def _tile_shape(conv, units, k_in, n_cols, T, layer=0, rates=0):
+    o12 = (Ct.c_int32 * 12)()
+    assert _lib().snn_debug_tile_shape(conv, units, k_in, n_cols, T, rates, layer, o12) == 0
+    return list(o12)
+
+
+def test_rpn_head_knobs(gpu_device, monkeypatch):
+    case = G.rpn_t_case(256, 8)
+    P = sum(case["N"] * h * w for h, w in case["shapes"])
+    assert _tile_shape(1, P, 256, 256, 8)[8] == 1
+    monkeypatch.setenv("SNN_SPARSE", "0")
+    assert _tile_shape(1, P, 256, 256, 8)[8] == 0
+    run_rpn(case, gpu_device, sparse=False)
+    for wn, mt in (("1", "4"), ("1", "2"), ("2", "4"), ("2", "2")):               # the WN / MT tile pairs of tests/test_gpu_tile_shapes.py (dense launches)
+        monkeypatch.setenv("SNN_BF16X3_WN", wn)
+        monkeypatch.setenv("SNN_BF16X3_MT", mt)
+        o = _tile_shape(1, P, 256, 256, 8)
+        assert o[8] == 0 and o[7] == int(wn) and o[0] == int(mt), o
+        run_rpn(case, gpu_device, sparse=False)
+    monkeypatch.delenv("SNN_BF16X3_WN")
+    monkeypatch.delenv("SNN_BF16X3_MT")
+    monkeypatch.delenv("SNN_SPARSE")
+    fat = _tile_shape(1, P, 256, 256, 8)[1]
+    monkeypatch.setenv("SNN_SPARSE_FAT", "0")
+    monkeypatch.setenv("SNN_SPARSE_FAT_CONV", "0")                   # (the conv's FAT shapes have a switch of their own)
+    o = _tile_shape(1, P, 256, 256, 8)
+    assert fat == 1 and o[8] == 1 and o[1] == 0, o
+    run_rpn(case, gpu_device, sparse=True)
+    monkeypatch.delenv("SNN_SPARSE_FAT")
+    monkeypatch.delenv("SNN_SPARSE_FAT_CONV")
+    monkeypatch.setenv("SNN_PLANES", "rm")                           # row-major planes: the sparse pair needs the word-major ones, so the dense launch runs
+    run_rpn(case, gpu_device, sparse=False)
+    monkeypatch.delenv("SNN_PLANES")
+    # the knob is read by the DENSE bf16x3 launch only (the sparse launchers choose their epilogue from T alone): run it where it acts -
+    # at T = 8 the dense tile has a straight-line epilogue instance, which the knob replaces by the guarded general form
+    monkeypatch.setenv("SNN_EPI_GENERAL", "1")
+    monkeypatch.setenv("SNN_SPARSE", "0")
+    run_rpn(case, gpu_device, sparse=False)
+
+
+def test_det_head_knobs(gpu_device, monkeypatch):
+    case = G.det_t_case(12)
+    R, D, Hd = case["R"], case["C"] * 49, case["Hd"]
+    assert _tile_shape(0, R, D, Hd, 12, 6)[8] == 1
+    monkeypatch.setenv("SNN_SPARSE", "0")
+    assert _tile_shape(0, R, D, Hd, 12, 6)[8] == 0
+    run_det(case, gpu_device, fc6_sparse=False)
+    for wn, mt in (("1", "4"), ("1", "2"), ("2", "4"), ("2", "2")):
+        monkeypatch.setenv("SNN_BF16X3_WN", wn)
+        monkeypatch.setenv("SNN_BF16X3_MT", mt)
+        o = _tile_shape(0, R, D, Hd, 12, 6)
+        assert o[8] == 0 and o[7] == int(wn) and o[0] == int(mt), o
+        run_det(case, gpu_device, fc6_sparse=False)
+    monkeypatch.delenv("SNN_BF16X3_WN")
+    monkeypatch.delenv("SNN_BF16X3_MT")
+    monkeypatch.delenv("SNN_SPARSE")
+    fat = _tile_shape(0, R, D, Hd, 12, 6)[1]
+    monkeypatch.setenv("SNN_SPARSE_FAT", "0")
+    o = _tile_shape(0, R, D, Hd, 12, 6)
+    assert fat == 1 and o[8] == 1 and o[1] == 0, o
+    run_det(case, gpu_device, fc6_sparse=True)
+    monkeypatch.delenv("SNN_SPARSE_FAT")
+    monkeypatch.setenv("SNN_PLANES", "rm")
+    run_det(case, gpu_device)
+    off3 = (Ct.c_uint64 * 3)()
+    _lib().snn_debug_last_det_planes(off3)
+    assert off3[2] == 0                                              # lif6's planes are rows, not word-major
+    monkeypatch.delenv("SNN_PLANES")
+    monkeypatch.setenv("SNN_EPI_GENERAL", "1")                       # as for the RPN: on the dense launches, where the knob is read (fc6 and fc7)
+    monkeypatch.setenv("SNN_SPARSE", "0")
+    run_det(case, gpu_device, fc6_sparse=False)
+
+
+# ---- the secondary sparse pass, and the feature types ----------------------------------------------------------------------------------
+def test_full_nibble_features_take_the_secondary_pass_everywhere(gpu_device):
+    run_rpn(G.rpn_full_nibble_case(), gpu_device, sparse=True)
+    run_det(G.det_full_nibble_case(), gpu_device, fc6_sparse=True)
+
+
+@pytest.mark.parametrize("feat", ["fp16", "bf16"])
+def test_half_precision_features(gpu_device, feat):
+    run_rpn(G.rpn_feat_case(feat), gpu_device, sparse=True)
+    run_det(G.det_feat_case(feat), gpu_device, fc6_sparse=True)
+
+
+def test_channels_last_features(gpu_device):
+    run_rpn(G.rpn_t_case(64, 8), gpu_device, sparse=True, nhwc=True)
+    run_det(G.det_t_case(12), gpu_device, fc6_sparse=True, nhwc=True)

@@ -3,7 +3,9 @@ ORACLE's tensors of the previous stage and compared with the oracle's next stage
 
   encoder kernels      bit-exact (element-wise fp32 arithmetic, same rounding sequence)
   LIF scan             bit-exact given identical input currents
-  conv / GEMM currents <= 1e-5 abs (fp32 summation order differs from oneDNN's — cannot be bit-exact)
+  conv / GEMM currents <= 1e-5 abs (fp32 summation order differs from oneDNN's: with arbitrary real-valued weights they cannot be
+                       bit-exact; on dyadic weight grids every partial sum is exact and they ARE - tests/test_gpu_exact_grid.py
+                       compares them with torch.equal and the hidden planes with zero flips)
   conv+LIF spikes      identical except neurons whose oracle margin |v_dec - theta| is below the
                        current tolerance at their FIRST differing step (flip budget)
   LI heads             <= 1e-5 abs
