@@ -47,7 +47,18 @@ typedef struct ihipStream_t* snn_stream_t;   /* == hipStream_t */
 /* Neuron constants.  The fp32 products are formed by the caller exactly as Norse forms them
  * (0-dim fp32 tensor arithmetic: dt * tau_mem_inv, -dt * tau_syn_inv) so that the element-wise
  * arithmetic is bit-identical to the reference's (norse lif.py / leaky_integrator.py; reference
- * call sites rpn.py:58,67,101,106,111,115, faster_rcnn.py:444-456,494-510). */
+ * call sites rpn.py:58,67,101,106,111,115, faster_rcnn.py:444-456,494-510).
+ * Semantics of one set (any finite values; the reference's are the comments on the fields):
+ *   - the encoder (lif_current_encoder) and the hidden LIF cells share v_leak, v_reset and both products; they differ in their
+ *     threshold only (v_th_enc / v_th_lif);
+ *   - the encoder's membrane starts at 0 whatever v_leak is (rpn.py:93, faster_rcnn.py:484); an LIF cell's membrane starts at v_leak and
+ *     its synaptic current at 0, so v_leak - v_th_lif > 0 fires every LIF neuron at step 0;
+ *   - the LI cells of the heads take the same two products with v_leak = 0 and start from zero state;
+ *   - the encoder resets arithmetically, v - (v - v_reset), the LIF cells to v_reset; spikes are (v - v_th > 0).
+ * No combination is refused.  The values choose the launch plan, never the result: zero rest and reset potentials run period planes, the
+ * threshold-table encoder where a table verifies for (dt_tau_mem, v_th_enc) (0 < dt_tau_mem < 1, v_th_enc > 0; else its recurrence) and
+ * the structured-sparse launches; any other rest / reset potential the op-for-op encoder and the dense launches; a spike at step 0 keeps
+ * step 0 in fc7's window.  Every plan is pinned to the parametrised oracle bit for bit (tests/test_gpu_neuron_constants.py). */
 typedef struct snn_params {
     float dt_tau_mem;      /* fl32(dt * tau_mem_inv)   = 0.1f for the reference (dt=0.001, 1/1e-2) */
     float neg_dt_tau_syn;  /* fl32(-dt * tau_syn_inv)  = -0.2f                  (1/5e-3)           */

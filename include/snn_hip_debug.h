@@ -33,6 +33,12 @@ int snn_debug_encoder_thresholds(const snn_params* p, float* th32);
  * instruction, period planes on the structured-sparse instruction, M-tile slots in use per work-group (sparse plan; else 0)}.
  * Returns 0, or -4 if no tile holds that many steps (the launch then takes the un-fused path). */
 int snn_debug_tile_shape(int conv, long long units, int k_in, int n_cols, int num_steps, int spike_rates, int layer, int32_t* out12);
+/* Introspection (tests): the form of the encoder kernel the calling thread's last encoder launch ran (stage entries, both heads, the
+ * RoIAlign feeds): 2 = period planes from the threshold table (zero rest / reset potentials and a table that verified for the call's
+ * (dt_tau_mem, v_th_enc)), 1 = the zero-rest recurrence (sub, mul, add, compare, select), 0 = the op-for-op form of Norse's
+ * lif_current_encoder (any other rest / reset potential, SNN_ENC_GENERIC=1; the un-fused RoIAlign encoders without a table).  -1 before
+ * the thread's first encoder launch.  Read-only. */
+int snn_debug_last_enc_mode(void);
 /* Introspection (tests, bench.py): 1 if the calling thread's last bf16x3 RPN conv + LIF enqueued the structured-sparse launch pair
  * (csrc/snn_sparse.h: planes e_3 .. on v_smfmac, no dense launch), 0 if it took the dense launch (SNN_SPARSE=0, conv T outside 5 .. 16, channel counts that are not multiples of 64, ...). */
 int snn_debug_last_conv_path(void);

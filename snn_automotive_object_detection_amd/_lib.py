@@ -43,6 +43,7 @@ class snn_rpn_post_level(C.Structure):
 DEBUG_SYMBOLS = {
     "snn_debug_reload_knobs": (None, []),
     "snn_debug_encoder_thresholds": (C.c_int, [C.POINTER(snn_params), C.POINTER(C.c_float)]),
+    "snn_debug_last_enc_mode": (C.c_int, []),
     "snn_debug_last_conv_path": (C.c_int, []),
     "snn_debug_last_fc6_path": (C.c_int, []),
     "snn_debug_last_det_planes": (None, [C.POINTER(C.c_uint64)]),
@@ -180,7 +181,7 @@ SYMBOLS = {
 }
 
 _LIB = None
-_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded")
+_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_debug_last_enc_mode")
 
 
 class SnnHipError(RuntimeError):
@@ -215,7 +216,8 @@ def load(build_if_missing: bool = True):
     for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
         if path != _build.LIB_PATH and (name.endswith("_typed") or name in _STATIC_PATH) and not hasattr(lib, name):
             continue                     # an A/B library from before the typed entry points: fp32 features only (half features: AttributeError);
-                                         # from before the static-shape path: the list API only
+                                         # from before the static-shape path: the list API only; from before snn_debug_last_enc_mode:
+                                         # no report of the encoder form
         fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

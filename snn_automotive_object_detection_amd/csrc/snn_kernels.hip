@@ -32,6 +32,7 @@ static thread_local char g_err[512] = "";
 static thread_local int g_last_fc_sparse = 0;      // ... the detector's fc6 + LIF
 static thread_local unsigned long long g_last_rpn_planes[3] = {0, 0, 0};      // workspace offset of the shared LIF's spike planes, blocks of four words?, positions
 static thread_local unsigned long long g_last_det_planes[3] = {0, 0, 0};      // workspace offsets of lif6's / lif7's spike planes, lif6 word-major?
+static thread_local int g_last_enc_mode = -1;      // ENC_* form of this thread's last encoder launch (snn_debug_last_enc_mode); -1: none yet
 static thread_local int g_last_conv_sparse = 0;    // did this thread's last RPN conv + LIF enqueue the sparse launch pair (snn_debug_last_conv_path)
 
 static int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -813,6 +814,7 @@ int snn_debug_clock_probe(unsigned long long* out2_dev, unsigned int ticks_100mh
     return 0;
 }
 
+int snn_debug_last_enc_mode(void) { return g_last_enc_mode; }
 int snn_debug_last_conv_path(void) { return g_last_conv_sparse; }
 int snn_debug_last_fc6_path(void) { return g_last_fc_sparse; }
 void snn_debug_last_rpn_planes(unsigned long long* out3) { if (out3) for (int i = 0; i < 3; ++i) out3[i] = g_last_rpn_planes[i]; }
@@ -1449,7 +1451,7 @@ int snn_encode_nchw_typed(const void* feat_v, int fdt, int N, int C, int H, int 
     NeuronP np = make_p(p, p->v_th_enc);
     if (knobs().stage_periods && enc_zero_rest(np)) np.v_fire = ENC_FIRED;      // (tests / tools: period planes)
     const EncTh* eth;
-    const int em = enc_mode(np, &eth);
+    const int em = g_last_enc_mode = enc_mode(np, &eth);
     const dim3 g(cdiv(HW, ENC_PB), cdiv(Cw, ENC_WB), N);
     launch_picked(encode_nchw_kernel(em, fdt), g, dim3(256), nhwc ? ENC_NHWC_LDS_BYTES(T, feat_elem_bytes(fdt)) : ENC_LDS_BYTES(T), (hipStream_t)s, feat, C,
                   HW, Cw, T, np, *eth, planes, plane_stride);
@@ -1490,7 +1492,7 @@ static int encode_rows_impl(const void* x_v, int R, int D, int T, const snn_para
         np.v_fire = ENC_FIRED;
     }
     const EncTh* eth;
-    const int em = enc_mode(np, &eth);
+    const int em = g_last_enc_mode = enc_mode(np, &eth);
     if (wm) {
         if (!encode_rows_wm_ok(x, D)) return fail(-1, "snn_encode_rows: word-major planes need D %% 32 == 0 and 16-byte aligned rows");
         const dim3 g(cdiv(Dw, 8), cdiv(R, 32));
@@ -1572,6 +1574,7 @@ static int roi_align_encode_impl(const snn_roi_level* levels_host, int n_levels,
         const EncTh* eth;
         if (enc_mode(a.p, &eth) == ENC_QUANT) { a.quant = 1; a.eth = *eth; }
     }
+    g_last_enc_mode = a.quant ? ENC_QUANT : ENC_GENERIC;        // (the RoIAlign encoders have two forms: the table, or enc_step op for op)
     // word-major planes: the table-driven kernel (sample geometry once per wave and RoI) wherever its 8-byte tap pairs and 32-bit
     // element offsets are valid; SNN_ROI_TAB=0 keeps the per-element form (bit-identical planes, A/B + test switch)
     bool tab_ok = wm && knobs().roi_tab;
@@ -2052,7 +2055,7 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         NeuronP np = make_p(p, p->v_th_enc);
         if (per) np.v_fire = ENC_FIRED;
         const EncTh* eth;
-        const int em = enc_mode(np, &eth);
+        const int em = g_last_enc_mode = enc_mode(np, &eth);
         const dim3 ge(blocks, cdiv(Cw, ENC_WB));
         uint32_t* const cmp_e = em == ENC_QUANT ? enc_cmp : nullptr;         // (the compressed-plane fold: period planes by thresholds only)
         launch_picked(encode_levels_kernel(em, fdt), ge, dim3(256), nhwc ? ENC_NHWC_LDS_BYTES(Tc, feat_elem_bytes(fdt)) : ENC_LDS_BYTES(Tc), s, el, C, Cw, Tc, np,
@@ -2662,6 +2665,7 @@ static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, i
         // were 9 us slower) - profiles/r5_encoder_nw_ab.txt
         const int nw = knobs().encp_nw ? (knobs().encp_nw == 4 ? 4 : 8) : (lds > 53 * 1024 ? 8 : 4);
         const void* kern = encode_rows_perm_kernel(rb, nw, fdt);
+        g_last_enc_mode = ENC_QUANT;                            // (det_fc6_folds: the folded encoder exists in the threshold form only)
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
         uint32_t* planes_f = (uint32_t*)((char*)ws + dp.o_enc);
@@ -2737,6 +2741,7 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
         const int n_cp = C / 64, n_items = fa.n_rg * 7;
         const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
         const size_t lds = (size_t)fa.T * (nhwc ? 7 : 7 + 8) * 4 * RW * 8;       // word pairs + raw ballots (channels-last: word pairs only)
+        g_last_enc_mode = ENC_QUANT;
         launch_picked(roi_align_encode_perm_kernel<RW>(fdt), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
         SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
         dp.bin_major = nhwc_raw;

@@ -13,9 +13,13 @@ import torch
 CUR_TOL = 1e-5            # the LI heads' bound of tests/test_gpu_stages.py (fp32 sums of <= 2048 products against fp64)
 
 
-def li_constants():
-    """(a, b) = (dt * tau_mem_inv, dt * tau_syn_inv) as fp32 products of 0-dim tensors, the way Norse and ops.make_params form them"""
-    return float(torch.tensor(0.001) * torch.tensor(100.0)), float(torch.tensor(0.001) * torch.tensor(200.0))
+def li_constants(constants=None):
+    """(a, b) = (dt * tau_mem_inv, dt * tau_syn_inv) as fp32 products of 0-dim tensors, the way Norse and ops.make_params form them;
+    ``constants`` (oracle.snn_oracle.NeuronConstants) defaults to the reference's dt = 1 ms, 100 / s, 200 / s"""
+    if constants is None:
+        return float(torch.tensor(0.001) * torch.tensor(100.0)), float(torch.tensor(0.001) * torch.tensor(200.0))
+    return (float(torch.tensor(constants.dt) * torch.tensor(constants.tau_mem_inv)),
+            float(torch.tensor(constants.dt) * torch.tensor(constants.tau_syn_inv)))
 
 
 # ---- layouts ------------------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import _exact_grid as G
+from tests import _neuron_constants as NC
 from tests._planes import CUR_TOL, head_det_planes, head_rpn_planes, li_constants, li_fp64
 from tests._util import dense_to_planes, nchw_to_rows, planes_to_dense
 
@@ -151,21 +152,38 @@ def _heads_w(case, precision):
     return w.to(torch.bfloat16).float() if precision == "bf16" else w
 
 
-def run_rpn(case, dev, precision="bf16x3", sparse=None, nhwc=False):
-    """both modes of RPNHeadSNN on a case: planes == the oracle's, counts == the oracle's, outputs at every position"""
+def _apply_constants(m, case):
+    """the case's neuron constants (tests/_exact_grid.NEURON_SETS; None: the reference's, nothing to do) on a head module, by the route
+    the set is listed with; returns the constants the LI bound is evaluated at"""
+    k = case.get("constants")
+    if k is not None:
+        NC.set_on_module(m, k, G.route_of(k))
+    return k
+
+
+def _assert_enc_mode(enc_mode):
+    if enc_mode is not None:
+        got = _lib().snn_debug_last_enc_mode()
+        assert got in (enc_mode if isinstance(enc_mode, tuple) else (enc_mode,)), "encoder form %d ran, expected %s" % (got, enc_mode)
+
+
+def run_rpn(case, dev, precision="bf16x3", sparse=None, nhwc=False, enc_mode=None):
+    """both modes of RPNHeadSNN on a case: planes == the oracle's, counts == the oracle's, outputs at every position.
+    ``enc_mode``: the encoder form(s) that must have run (snn_debug_last_enc_mode)"""
     import snn_automotive_object_detection_amd as pkg
     C, A, T, N = case["C"], case["A"], case["T"], case["N"]
     m = pkg.RPNHeadSNN(C, A, T).to(dev)
     m.precision, m.li_order = precision, case["li_order"]
     m.load_state_dict({"shared_conv.weight": case["w_shared"], "conv_cls.weight": case["w_cls"], "conv_bbox.weight": case["w_bbox"]})
     feats = [_features(f, dev, case["feat"], nhwc) for f in case["feats"]]
-    a, b = li_constants()
+    a, b = li_constants(_apply_constants(m, case))
     for rates in (False, True):
         m.spike_rates = rates
         out = m(feats)
         assert m._resolve_precision() == precision
         if sparse is not None:
             assert _lib().snn_debug_last_conv_path() == int(sparse), "not the launch this test is about"
+        _assert_enc_mode(enc_mode)
         got = planes_to_dense(head_rpn_planes(dev, T, C), C)
         diff = got != case["spk"]
         assert not diff.any(), "hidden planes differ from the oracle's at (step, position, channel) %s ... (%d in all)" % (np.argwhere(diff)[:4].tolist(), int(diff.sum()))
@@ -175,14 +193,17 @@ def run_rpn(case, dev, precision="bf16x3", sparse=None, nhwc=False):
         pos = 0
         for l, (H, W) in enumerate(case["shapes"]):
             o = torch.cat([out[0][l], out[1][l]], dim=1).permute(0, 2, 3, 1).reshape(N * H * W, 5 * A).double().cpu().numpy()
-            assert np.abs(o - last[T - 1, pos:pos + N * H * W]).max() <= CUR_TOL
             e = torch.cat([case["logits"][l], case["bbox"][l]], dim=1).permute(0, 2, 3, 1).reshape(N * H * W, 5 * A).numpy()
+            if case.get("constants") is not None:
+                print("rpn level %d: |out - fp64| %.3g, |out - oracle| %.3g, |out| %.3g" % (
+                    l, np.abs(o - last[T - 1, pos:pos + N * H * W]).max(), np.abs(o - e).max(), np.abs(o).max()))
+            assert np.abs(o - last[T - 1, pos:pos + N * H * W]).max() <= CUR_TOL
             assert np.abs(o - e).max() <= TOL
             pos += N * H * W
     return m
 
 
-def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False):
+def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False, enc_mode=None):
     import snn_automotive_object_detection_amd as pkg
     R, C, Hd, K, T = case["R"], case["C"], case["Hd"], case["K"], case["T"]
     d = pkg.FastRCNNPredictorSNNFull(C * 49, Hd, K, T).to(dev)
@@ -191,7 +212,7 @@ def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False):
     x = _features(case["x"], dev, case["feat"], nhwc)
     tr = case["trace"]
     e6, e7 = tr["spk6"].numpy(), tr["spk7"].numpy()
-    a, b = li_constants()
+    a, b = li_constants(_apply_constants(d, case))
     for rates in (False, True):
         d.spike_rates = rates
         out = d(x)
@@ -199,6 +220,7 @@ def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False):
         if fc6_sparse is not None:                                   # (a pair: plain forward, spike-rate mode)
             want = fc6_sparse[int(rates)] if isinstance(fc6_sparse, tuple) else fc6_sparse
             assert _lib().snn_debug_last_fc6_path() == int(want), "not the launch this test is about"
+        _assert_enc_mode(enc_mode)
         p6, p7 = head_det_planes(dev, T, Hd, R)
         n6 = T if rates else T - 1                                   # (without the rates lif6's spikes of the last step are never read and not formed)
         g6, g7 = planes_to_dense(p6, Hd), planes_to_dense(p7, Hd)
@@ -211,6 +233,9 @@ def run_det(case, dev, precision="bf16x3", fc6_sparse=None, nhwc=False):
             continue                                                 # (in this mode the detector's forward returns ONLY the rate rows: no cls / bbox to compare)
         o = torch.cat([out[0], out[1]], dim=1).double().cpu().numpy()
         last, _ = li_fp64(e7, _heads_w(case, precision), a, b, case["li_order"])
+        if case.get("constants") is not None:
+            print("det: |out - fp64| %.3g, |out - oracle| %.3g, |out| %.3g" % (
+                np.abs(o - last[T - 1]).max(), np.abs(o - torch.cat([case["cls"], case["bbox"]], dim=1).numpy()).max(), np.abs(o).max()))
         assert np.abs(o - last[T - 1]).max() <= CUR_TOL
         assert np.abs(o - torch.cat([case["cls"], case["bbox"]], dim=1).numpy()).max() <= TOL
     return d

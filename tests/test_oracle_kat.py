@@ -185,3 +185,114 @@ def test_encoder_on_non_finite_and_extreme_inputs_kat():
     with np.errstate(invalid="ignore"):
         first_by_0 = x.numpy() >= np.float32(th[0])
     assert first_by_0.tolist() == [True, False, False, True, False, True]
+
+
+# ---- neuron constants other than the reference's: answers worked out by hand (decimal arithmetic; none produced by the restatement) ---------
+def _K(**kw):
+    from oracle import snn_oracle as OR
+    return OR.NeuronConstants(**kw)
+
+
+def test_default_neuron_constants_are_the_reference_values():
+    from oracle import snn_oracle as OR
+    k = OR.NeuronConstants()
+    assert tuple(k) == (0.25, 0.1, 0.0, 0.0, 0.001, 100.0, 200.0) and k == OR.DEFAULT_CONSTANTS and hash(k) == hash(OR.NeuronConstants())
+    assert 1.0 / 1e-2 == 100.0 and 1.0 / 5e-3 == 200.0
+    assert k.ca == float(np.float32(0.1)) and k.cb == float(np.float32(-0.2))
+    # the parameter tuples the cells get are the ones the fixed call sites used to build, value for value
+    p = k.lif_parameters(k.v_th_lif)
+    q = NR.LIFParameters(alpha=100, v_th=torch.tensor(0.1))
+    for name in ("tau_syn_inv", "tau_mem_inv", "v_leak", "v_th", "v_reset"):
+        a, b = getattr(p, name), getattr(q, name)
+        assert a.dtype == b.dtype == torch.float32 and a.dim() == 0 and torch.equal(a, b), name
+    li = k.li_parameters()
+    for name in ("tau_syn_inv", "tau_mem_inv", "v_leak"):
+        assert torch.equal(getattr(li, name), getattr(NR.LIParameters(), name))
+
+
+def test_encoder_with_a_reset_potential_kat():
+    """v_reset = -0.05, v_th = 0.25, dt * tau_mem_inv = 0.1, constant input 1: v = 0.1, 0.19, 0.271 -> spike, v - (v + 0.05) = -0.05;
+    then -0.05 + 0.1 * 1.05 = 0.055, 0.1495, 0.23455, 0.311095 -> spike: the first spike after 3 steps, then every 4 (every 3 at
+    v_reset = 0).  The membrane after a spike is the fp32 value of v - (v - v_reset), which is NOT the float -0.05 for every v."""
+    from oracle import snn_oracle as OR
+    k = _K(v_reset=-0.05)
+    z = OR.encoder_spikes(torch.ones(1), 11, k)[:, 0]
+    assert z.tolist() == [0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1]
+    assert OR.encoder_spikes(torch.ones(1), 11)[:, 0].tolist() == [0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0]
+    p, v, vs = k.lif_parameters(k.v_th_enc), torch.zeros(1), []
+    for _ in range(7):
+        _, v = NR.lif_current_encoder(torch.ones(1), v, p, k.dt)
+        vs.append(float(v))
+    np.testing.assert_allclose(vs, [0.1, 0.19, -0.05, 0.055, 0.1495, 0.23455, -0.05], atol=1e-6)
+    # the arithmetic reset, in numpy's fp32: v = 0.9 crosses at once; 0.9f + 0.05f rounds, and 0.9f minus that is one ulp off -0.05f
+    f = np.float32
+    v1 = f(f(0.0) + f(f(0.1) * f(f(f(0.0) - f(0.0)) + f(9.0))))
+    want = f(v1 - f(v1 - f(-0.05)))
+    z, v = NR.lif_current_encoder(torch.full((1,), 9.0), torch.zeros(1), p, k.dt)
+    assert float(z) == 1.0 and np.float32(float(v)).view(np.uint32) == want.view(np.uint32)
+    assert want != f(-0.05)                                           # (so "reset to exactly v_reset" is a different encoder)
+
+
+def test_encoder_starts_at_zero_not_at_the_rest_potential_kat():
+    """v_leak = 0.05, input 2.4: from v = 0 (rpn.py:93) the membrane is 0.1 * 2.45 = 0.245 < 0.25, then 0.245 + 0.1 * 2.205 = 0.4655 ->
+    spike, reset to v - (v - 0) = 0: spikes at steps 1, 3, 5.  From v = v_leak it would be 0.05 + 0.1 * 2.4 = 0.29: a spike at step 0."""
+    from oracle import snn_oracle as OR
+    assert OR.encoder_spikes(torch.full((1,), 2.4), 6, _K(v_leak=0.05))[:, 0].tolist() == [0, 1, 0, 1, 0, 1]
+    assert OR.encoder_spikes(torch.full((1,), 2.4), 6)[:, 0].tolist() == [0, 1, 0, 1, 0, 1]          # (0.24, 0.456: the same train at v_leak = 0)
+    assert OR.encoder_spikes(torch.full((1,), 2.46), 3, _K(v_leak=0.05))[:, 0].tolist() == [1, 1, 1]  # 0.1 * 2.51 = 0.251
+    assert OR.encoder_spikes(torch.full((1,), 2.46), 3)[:, 0].tolist() == [0, 1, 0]                   # 0.246; 0.246 + 0.2214
+
+
+def test_lif_rest_potential_above_threshold_fires_at_step_0_kat():
+    """v_leak = 0.2 > v_th = 0.1: the cell starts at v = v_leak, so v_dec = 0.2 at step 0 -> spike, v = v_reset = 0.  Without input the
+    membrane then climbs back towards the rest potential, 0.2 (1 - 0.9^n) = 0.02, 0.038, 0.0542, 0.06878, 0.081902, 0.0937118,
+    0.10434062 -> the next spike at step 7.  With input 1: i = 1, 1.8, 2.44, 2.952 and v_dec = 0.12, 0.2, 0.264: a spike every step."""
+    from oracle import snn_oracle as OR
+    k = _K(v_leak=0.2)
+    z, state, vdec = OR.lif_scan_from_currents(torch.zeros(9, 1), constants=k)
+    assert z[:, 0].tolist() == [1, 0, 0, 0, 0, 0, 0, 1, 0]
+    np.testing.assert_allclose(vdec[:8, 0].numpy(), [0.2, 0.02, 0.038, 0.0542, 0.06878, 0.081902, 0.0937118, 0.10434062], atol=1e-6)
+    z, state, vdec = OR.lif_scan_from_currents(torch.ones(4, 1), constants=k)
+    assert z[:, 0].tolist() == [1, 1, 1, 1]
+    np.testing.assert_allclose(vdec[:, 0].numpy(), [0.2, 0.12, 0.2, 0.264], atol=1e-6)
+    np.testing.assert_allclose([float(state.v), float(state.i)], [0.0, 2.952], atol=1e-6)
+    # a threshold below the rest potential 0 does the same: v_dec = 0 > -0.05 at step 0
+    assert OR.lif_scan_from_currents(torch.zeros(2, 1), constants=_K(v_th_lif=-0.05))[0][:, 0].tolist() == [1, 1]
+    assert OR.lif_scan_from_currents(torch.zeros(2, 1))[0][:, 0].tolist() == [0, 0]
+
+
+def test_lif_rest_and_reset_potentials_kat():
+    """v_leak = 0.04, v_reset = -0.03, v_th = 0.1, input 0.2 every step, (z, v, i) after each step:
+    v_dec = 0.04;  0.04 + 0.1 (0 + 0.2) = 0.06;  0.06 + 0.1 (-0.02 + 0.36) = 0.094;  0.094 + 0.1 (-0.054 + 0.488) = 0.1374 -> spike, v = -0.03;
+    -0.03 + 0.1 (0.07 + 0.5904) = 0.03604;  i = 0.2, 0.36, 0.488, 0.5904, 0.67232"""
+    k = _K(v_leak=0.04, v_reset=-0.03)
+    cell = NR.LIFCell(p=k.lif_parameters(k.v_th_lif), dt=k.dt)
+    state, out = None, []
+    for _ in range(5):
+        z, state = cell(torch.full((1,), 0.2), state)
+        out.append((float(z), float(state.v), float(state.i)))
+    expect = [(0, 0.04, 0.2), (0, 0.06, 0.36), (0, 0.094, 0.488), (1, -0.03, 0.5904), (0, 0.03604, 0.67232)]
+    np.testing.assert_allclose(np.array(out), np.array(expect), atol=1e-6)
+
+
+def test_time_step_and_time_constants_kat():
+    """dt = 2 ms: ca = 0.2, cb = -0.4; LIF at v_th = 0.1 on input 1: v_dec = 0, 0.2 -> spike, 0.2 * 1.6 = 0.32 -> spike; i = 1, 1.6, 1.96.
+    tau_mem_inv = 150, tau_syn_inv = 120 on the LI cell (jump first), input 1: i = 1, v = 0.15, i = 0.88; i = 1.88, v = 0.15 + 0.15 * 1.73 =
+    0.4095, i = 1.6544; i = 2.6544, v = 0.4095 + 0.15 * 2.2449 = 0.746235: last 0.746235, sum over t 1.305735."""
+    from oracle import snn_oracle as OR
+    k = _K(dt=0.002)
+    assert k.ca == float(np.float32(0.002) * np.float32(100.0)) and k.cb == float(-np.float32(0.002) * np.float32(200.0))
+    z, state, vdec = OR.lif_scan_from_currents(torch.ones(3, 1), constants=k)
+    assert z[:, 0].tolist() == [0, 1, 1]
+    np.testing.assert_allclose(vdec[:, 0].numpy(), [0.0, 0.2, 0.32], atol=1e-6)
+    np.testing.assert_allclose(float(state.i), 1.96, atol=1e-6)
+    k = _K(tau_mem_inv=150.0, tau_syn_inv=120.0)
+    assert k.ca == float(np.float32(0.001) * np.float32(150.0)) and k.cb == float(-np.float32(0.001) * np.float32(120.0))
+    last, acc = OR.li_last_from_spikes(torch.ones(3, 1, 1), torch.ones(1, 1), constants=k)
+    np.testing.assert_allclose([float(last), float(acc)], [0.746235, 1.305735], atol=1e-6)
+    last, _ = OR.li_last_from_spikes(torch.ones(3, 1, 1), torch.ones(1, 1), "voltage_first", constants=k)
+    np.testing.assert_allclose(float(last), 0.4095, atol=1e-6)      # (the input of step t reaches the membrane one step later)
+    # the LI cells ignore the rest and reset potentials: v_leak = 0 there
+    a, _ = OR.li_last_from_spikes(torch.ones(3, 1, 1), torch.ones(1, 1), constants=_K(v_leak=0.2, v_reset=-0.05))
+    b, _ = OR.li_last_from_spikes(torch.ones(3, 1, 1), torch.ones(1, 1))
+    assert torch.equal(a, b)
