@@ -269,7 +269,12 @@ int snn_det_rates(int R, int D, int Hd, int K, int K4, int T, int only_one_bbox,
 /* ---- greedy (batched) NMS for the callers either side of the heads (rpn.py:517, roi_heads.py:1160-1161) ----
  * boxes [n][4] already sorted by decreasing score; category (nullable) restricts suppression to equal values
  * (level for the RPN, class for the detector).  keep_out receives up to max_keep indices into the SORTED order,
- * in that order; *n_keep_out their number (device memory).  n <= 16384. */
+ * in that order; *n_keep_out their number (device memory).  n <= 16384.
+ * Comparison rule (here and for the nms_thresh of snn_rpn_proposals / snn_det_postprocess / snn_det_postprocess_padded): a box is
+ * suppressed when the fp32 IoU is > iou_threshold, compared as floats.  The parity target (torchvision's CPU kernel) compares the
+ * float IoU with a DOUBLE threshold t; to get its decisions pass the LARGEST fp32 <= t, not the nearest one - for a float IoU,
+ * `iou > t` in double is `iou > that fp32`.  The nearest fp32 lies above 0.3, 0.6, 0.8 (...) and would keep a pair whose IoU
+ * equals it.  ops.nms_threshold_f32 does this for every Python caller. */
 size_t snn_nms_workspace_bytes(int n);
 int snn_nms_sorted(const float* boxes_sorted, const int* category_sorted, int n, float iou_threshold, int max_keep,
                    int* keep_out, int* n_keep_out, void* workspace, size_t workspace_bytes, snn_stream_t stream);

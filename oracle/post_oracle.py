@@ -28,9 +28,13 @@ def _flatten_level(layer: Tensor, C: int) -> Tensor:
 
 def rpn_proposals(objectness: List[Tensor], pred_bbox_deltas: List[Tensor], image_tensor_hw: Tuple[int, int],
                   image_sizes: List[Tuple[int, int]], anchor_sizes, aspect_ratios, pre_nms_top_n: int, post_nms_top_n: int,
-                  nms_thresh: float, score_thresh: float = 0.0, min_size: float = 1e-3, stats: dict = None):
+                  nms_thresh: float, score_thresh: float = 0.0, min_size: float = 1e-3, stats: dict = None,
+                  stable_topk: bool = False):
     """objectness[l] [N, A, H_l, W_l], pred_bbox_deltas[l] [N, 4A, H_l, W_l] (what the head returns, rpn.py:613).
-    Returns (boxes per image, scores per image, [{'proposals', 'objectness'} per image]) like rpn.py:692-703."""
+    Returns (boxes per image, scores per image, [{'proposals', 'objectness'} per image]) like rpn.py:692-703.
+    ``stable_topk``: the per-level top-k is the first k of a STABLE descending sort (by logit, then by element index) instead of
+    objectness.topk, which leaves the choice and order of equal logits unspecified - the order the HIP selection documents
+    (k_topk_gather / k_topk_sort).  Without equal logits inside a level both give the same candidates."""
     num_images = objectness[0].shape[0]
     feats = [torch.empty((num_images, 1) + tuple(o.shape[-2:])) for o in objectness]
     images = TV.ImageList(torch.empty((num_images, 3) + tuple(image_tensor_hw)), image_sizes)
@@ -47,7 +51,10 @@ def rpn_proposals(objectness: List[Tensor], pred_bbox_deltas: List[Tensor], imag
     top, offset = [], 0
     for ob in obj.split(num_anchors_per_level, 1):                                              # rpn.py:403-416
         k = min(pre_nms_top_n, ob.shape[1])
-        top.append(ob.topk(k, dim=1)[1] + offset)
+        if stable_topk:
+            top.append(torch.sort(ob, dim=1, descending=True, stable=True)[1][:, :k] + offset)
+        else:
+            top.append(ob.topk(k, dim=1)[1] + offset)
         offset += ob.shape[1]
     top = torch.cat(top, dim=1)
     bi = torch.arange(num_images)[:, None]

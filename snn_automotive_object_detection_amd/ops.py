@@ -3,6 +3,7 @@ memory, the current HIP stream, nothing else.  Every function raises if the inpu
 tensor — there is no CPU or eager fallback."""
 import ctypes as C
 import numbers
+import struct
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -864,6 +865,20 @@ def det_head_forward_roialign_readouts(feats, scales, rois, roi_batch, roi_level
 # ---------------------------------------------------------------------------------------------
 # greedy / batched NMS (glue on either side of the heads)
 # ---------------------------------------------------------------------------------------------
+def nms_threshold_f32(t: float) -> float:
+    """The largest fp32 number <= t.  The parity target (torchvision's CPU kernel) compares a FLOAT IoU with the DOUBLE threshold;
+    the kernels compare with a float.  For a float IoU, ``iou > t`` in double is the same as ``iou > f`` with f the largest fp32 <= t,
+    whereas the nearest fp32 lies ABOVE decimals such as 0.3, 0.6 and 0.8 and would keep a pair whose IoU equals it.  Every NMS
+    threshold that crosses into the library goes through here."""
+    t = float(t)
+    f = C.c_float(t).value                   # nearest fp32
+    if f > t:                                # rounded up: one fp32 step down
+        bits = struct.unpack("<I", struct.pack("<f", f))[0]
+        bits = bits - 1 if f > 0.0 else (bits + 1 if f < 0.0 else 0x80000001)
+        f = struct.unpack("<f", struct.pack("<I", bits))[0]
+    return f
+
+
 def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: Optional[torch.Tensor], iou_threshold: float,
                 max_keep: Optional[int] = None) -> torch.Tensor:
     """indices of the kept boxes, by decreasing score; suppression only between boxes of equal idxs"""
@@ -879,7 +894,7 @@ def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: Optional[torch.
     keep = torch.empty((max_keep,), dtype=torch.int32, device=boxes.device)
     n_keep = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
     ws = _WS.get(boxes.device, lib.snn_nms_workspace_bytes(n))
-    _lib.check(lib.snn_nms_sorted(_ptr(b), _ptr(cat), n, float(iou_threshold), max_keep, _ptr(keep), _ptr(n_keep), _ptr(ws),
+    _lib.check(lib.snn_nms_sorted(_ptr(b), _ptr(cat), n, nms_threshold_f32(iou_threshold), max_keep, _ptr(keep), _ptr(n_keep), _ptr(ws),
                                   ws.numel(), _stream()), "snn_nms_sorted")
     k = int(n_keep.item())
     return order[keep[:k].to(torch.int64)]
@@ -899,7 +914,7 @@ def nms_keep_mask(boxes: torch.Tensor, scores: torch.Tensor, idxs: Optional[torc
     keep = torch.full((n,), n, dtype=torch.int32, device=boxes.device)      # unused slots point at a dummy element
     n_keep = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
     ws = _WS.get(boxes.device, lib.snn_nms_workspace_bytes(n))
-    _lib.check(lib.snn_nms_sorted(_ptr(b), _ptr(cat), n, float(iou_threshold), n, _ptr(keep), _ptr(n_keep), _ptr(ws),
+    _lib.check(lib.snn_nms_sorted(_ptr(b), _ptr(cat), n, nms_threshold_f32(iou_threshold), n, _ptr(keep), _ptr(n_keep), _ptr(ws),
                                   ws.numel(), _stream()), "snn_nms_sorted")
     kept = torch.zeros((n + 1,), dtype=torch.bool, device=boxes.device)
     kept[keep.to(torch.int64)] = True
@@ -960,7 +975,7 @@ def rpn_proposals(logits: Sequence[torch.Tensor], deltas: Sequence[torch.Tensor]
     pre_b = torch.empty((N, K, 4), dtype=torch.float32, device=dev) if want_pre else None
     pre_p = torch.empty((N, K), dtype=torch.float32, device=dev) if want_pre else None
     ws = _WS.get(dev, lib.snn_rpn_proposals_workspace_bytes(N, K))
-    _lib.check(lib.snn_rpn_proposals(lv, L, N, A, hw, int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh),
+    _lib.check(lib.snn_rpn_proposals(lv, L, N, A, hw, int(pre_nms_top_n), int(post_nms_top_n), nms_threshold_f32(nms_thresh),
                                      float(score_thresh), float(min_size), _ptr(boxes), _ptr(scores), _ptr(counts),
                                      _ptr(pre_b), _ptr(pre_p), _ptr(ws), ws.numel(), _stream()), "snn_rpn_proposals")
     return boxes, scores, counts, pre_b, pre_p
@@ -997,7 +1012,7 @@ def det_postprocess(class_logits: torch.Tensor, box_regression: torch.Tensor, pr
     hw = (C.c_float * (2 * N))(*[float(v) for s in image_sizes for v in (s[0], s[1])])
     ws = _WS.get(dev, max(1, lib.snn_det_postprocess_workspace_bytes(N, rmax, K)))
     bw = (C.c_float * 4)(*[float(v) for v in box_weights])
-    _lib.check(lib.snn_det_postprocess(_ptr(lg), _ptr(dl), _ptr(pr), rpi, N, K, hw, bw, float(score_thresh), float(nms_thresh),
+    _lib.check(lib.snn_det_postprocess(_ptr(lg), _ptr(dl), _ptr(pr), rpi, N, K, hw, bw, float(score_thresh), nms_threshold_f32(nms_thresh),
                                        int(detections_per_img), float(min_size), _ptr(all_scores), _ptr(all_boxes),
                                        _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(counts), cap, _ptr(ws), ws.numel(),
                                        _stream()), "snn_det_postprocess")
@@ -1059,7 +1074,7 @@ def det_postprocess_padded(class_logits: torch.Tensor, box_regression: torch.Ten
     ws = _WS.get(dev, max(1, lib.snn_det_postprocess_workspace_bytes(N, cap, K)))
     bw = (C.c_float * 4)(*[float(v) for v in box_weights])
     _lib.check(lib.snn_det_postprocess_padded(_ptr(lg), _ptr(dl), _ptr(pr), _ptr(cn), N, cap, K, hw, bw, float(score_thresh),
-                                              float(nms_thresh), int(detections_per_img), float(min_size), _ptr(all_scores),
+                                              nms_threshold_f32(nms_thresh), int(detections_per_img), float(min_size), _ptr(all_scores),
                                               _ptr(all_boxes), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(out_counts), D, _ptr(ws),
                                               ws.numel(), _stream()), "snn_det_postprocess_padded")
     return boxes, scores, labels, out_counts, all_scores, all_boxes

@@ -41,7 +41,8 @@ def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
         return torch.empty((0,), dtype=torch.int64, device=boxes.device)
     order = scores.argsort(descending=True, stable=True)
     b = boxes[order]
-    sup = torch.triu(box_iou(b, b) > iou_threshold, diagonal=1)          # sup[j, i]: j (better) suppresses i
+    # (the parity target, torchvision's CPU kernel, compares the FLOAT IoU with the DOUBLE threshold: 0.3 is not the fp32 nearest to it)
+    sup = torch.triu(box_iou(b, b).double() > iou_threshold, diagonal=1)  # sup[j, i]: j (better) suppresses i
     supf = sup.to(torch.float32)
     keep = torch.ones(n, dtype=torch.bool, device=boxes.device)
     for _ in range(n):

@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 
 def _greedy(boxes, scores, idxs, thr):
     order = scores.argsort(descending=True, stable=True).tolist()
-    iou = B.box_iou(boxes, boxes)
+    iou = B.box_iou(boxes, boxes).double()                     # float IoU against the double threshold, as the parity target compares
     keep = []
     while order:
         i = order.pop(0)
@@ -41,7 +41,7 @@ def _greedy_vec(boxes, scores, idxs, thr):
     """the same greedy definition with one vector operation per candidate (for the large cases)"""
     order = scores.argsort(descending=True, stable=True)
     b, c = boxes[order], idxs[order]
-    iou = B.box_iou(b, b)
+    iou = B.box_iou(b, b).double()
     sup = (iou > thr) & (c[:, None] == c[None, :])
     alive = torch.ones(len(order), dtype=torch.bool)
     keep = []
