@@ -514,6 +514,40 @@ int snn_det_head_forward_roialign_readouts_typed(const snn_roi_level* levels_hos
                                                  int w6_inner, const void* w7_packed, const float* w_heads_packed, float* out_cls,
                                                  float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls,
                                                  float* sum_bbox, void* workspace, size_t workspace_bytes, snn_stream_t stream);
+/* ---- conv route of the RPN head (opt-in, per call) -------------------------------
+ * The shared 3x3 conv + LIF has two launch plans for the bf16x3 family: the structured-sparse one (period planes e_3 .. compressed; its cost
+ * grows with the share of 16-row tiles that hold a third or fourth spike of one period in a nibble) and the all-dense one (cost independent of
+ * the input).  snn_rpn_head_forward_routed is snn_rpn_head_forward_stages_typed at SNN_STAGE_ALL with the choice made per call:
+ *   SNN_ROUTE_SPARSE  today's plan: the launches of snn_rpn_head_forward, bit for bit
+ *   SNN_ROUTE_DENSE   the all-dense plan for this call (what SNN_SPARSE=0 selects for a process), bit for bit
+ *   SNN_ROUTE_AUTO    decided ON THE DEVICE from the input, no host read: the encoder leaves every period plane raw; one launch compresses
+ *                     the planes e_3 .. and counts, with integer atomics, the HITS among the BLOCKS - block = 16 consecutive rows of the
+ *                     padded row space (aligned to 16 within the Pe = sum N (H + 2)(W + 2) rows of a word plane; blocks run across image
+ *                     and level boundaries and include halo rows) x one 64-channel word pair x one compressed plane; hit = a block in which
+ *                     some row's secondary-occupancy dword is non-zero; one thread sets route = (float)hits > crossover * (float)blocks ? 1 : 0;
+ *                     then BOTH conv launches are enqueued and the one whose route was not taken leaves at entry.  The route is a function
+ *                     of the input alone; the two sides write the same spike-plane layout and may differ only where the sparse and the dense
+ *                     plan may (threshold ties of the fp32 sums taken in another order).  crossover <= -1 always takes the dense side,
+ *                     crossover >= 1 never does.
+ * route_stat (device, int32[4], written on `stream`; nullable unless AUTO) = {hits, blocks, route taken (0 sparse / 1 dense), 0}.
+ * Where the call's plan is not the sparse one anyway (SNN_PRECISION_F32 / F32_STRICT / MXFP6, T outside 5 .. 16, a channel count whose padded
+ * words are odd in number or whose 64-column blocks are not 1, 2 or 4 - 3, 192, 320 -, non-zero rest or reset potentials, knobs), all three
+ * routes run that plan and route_stat = {0, 0, 1, 0}.  In spike-rate mode (spike_counts != NULL) all three routes run the plan of
+ * snn_rpn_head_forward and route_stat = {0, 0, 0, 0}.  SPARSE and DENSE count nothing either: route_stat = {0, 0, 0 / 1, 0}.
+ * The workspace is the plain forward's (its plane sets hold the raw planes of every period and the compressed planes; the gate word is
+ * route_stat[2]); the _routed size query exists so that this can change.  An unknown route, a null route_stat with AUTO and a workspace
+ * below the query's size return -1 with nothing enqueued.  SNN_ROUTE_DEFAULT_CROSSOVER: see profiles/route_crossover.txt. */
+#define SNN_ROUTE_SPARSE 0
+#define SNN_ROUTE_DENSE 1
+#define SNN_ROUTE_AUTO 2
+#define SNN_ROUTE_DEFAULT_CROSSOVER 0.357f
+size_t snn_rpn_head_workspace_bytes_routed(const snn_rpn_level* levels_host, int n_levels, int C, int A, int T, int precision, int route);
+int snn_rpn_head_forward_routed(const snn_rpn_level* levels_host, int feat_dtype, int n_levels, int C, int A, int T,
+                                const snn_params* p_host, const void* w_shared_packed, const float* w_heads_packed,
+                                float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                                float* sum_bbox, void* workspace, size_t workspace_bytes, int route, float crossover,
+                                int32_t* route_stat, snn_stream_t stream);
+
 /* the two stage-level calls the tests compare planes through */
 int snn_encode_nchw_typed(const void* feat, int feat_dtype, int N, int C, int H, int W, int T, const snn_params* p_host,
                           uint32_t* planes, size_t plane_stride_words, snn_stream_t stream);

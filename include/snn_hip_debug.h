@@ -40,7 +40,8 @@ int snn_debug_tile_shape(int conv, long long units, int k_in, int n_cols, int nu
  * the thread's first encoder launch.  Read-only. */
 int snn_debug_last_enc_mode(void);
 /* Introspection (tests, bench.py): 1 if the calling thread's last bf16x3 RPN conv + LIF enqueued the structured-sparse launch pair
- * (csrc/snn_sparse.h: planes e_3 .. on v_smfmac, no dense launch), 0 if it took the dense launch (SNN_SPARSE=0, conv T outside 5 .. 16, channel counts that are not multiples of 64, ...). */
+ * (csrc/snn_sparse.h: planes e_3 .. on v_smfmac, no dense launch), 0 if it took the dense launch (SNN_SPARSE=0, conv T outside 5 .. 16, channel counts that are not multiples of 64, ...),
+ * 2 if it enqueued both behind the gate word of SNN_ROUTE_AUTO (snn_rpn_head_forward_routed: route_stat[2] says which one computed). */
 int snn_debug_last_conv_path(void);
 int snn_debug_last_fc6_path(void);      /* the same for the detector head's fc6 + LIF */
 /* Introspection (parity tests): where the calling thread's last detector-head forward left its hidden spike planes in the caller's

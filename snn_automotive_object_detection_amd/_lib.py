@@ -16,6 +16,8 @@ FEAT_DTYPES = {"f32": 0, "f16": 1, "bf16": 2}          # SNN_FEAT_*
 FEAT_NHWC = 16                                            # SNN_FEAT_NHWC: layout bit, OR-ed into a FEAT_DTYPES code (channels-last maps)
 NO_TYPED_KERNEL = 1                                       # SNN_STATUS_NO_TYPED_KERNEL: nothing was enqueued; widen and call with "f32"
 PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3, "bf16": 4}
+CONV_ROUTES = {"sparse": 0, "dense": 1, "auto": 2}      # SNN_ROUTE_*
+ROUTE_DEFAULT_CROSSOVER = 0.357                            # SNN_ROUTE_DEFAULT_CROSSOVER (tests/test_conv_route_cpu.py compares it with the header)
 
 
 class snn_params(C.Structure):
@@ -175,6 +177,13 @@ SYMBOLS = {
     "snn_det_head_forward_roialign_readouts_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                                C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.POINTER(snn_params),
                                                                C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    # the RPN head with its conv route chosen per call (sparse / dense / decided on the device): the typed forward's arguments without the
+    # stage mask, then route, crossover, route_stat (device int32[4])
+    "snn_rpn_head_workspace_bytes_routed": (C.c_size_t, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "snn_rpn_head_forward_routed": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(snn_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float,
+                                              C.c_void_p, c_stream]),
     "snn_encode_nchw_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(snn_params), C.c_void_p, C.c_size_t, c_stream]),
     "snn_roi_align_encode_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
@@ -214,10 +223,10 @@ def load(build_if_missing: bool = True):
                           "there is no CPU fallback" % path)
     lib = C.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
-        if path != _build.LIB_PATH and (name.endswith("_typed") or name in _STATIC_PATH) and not hasattr(lib, name):
+        if path != _build.LIB_PATH and (name.endswith("_typed") or name.endswith("_routed") or name in _STATIC_PATH) and not hasattr(lib, name):
             continue                     # an A/B library from before the typed entry points: fp32 features only (half features: AttributeError);
                                          # from before the static-shape path: the list API only; from before snn_debug_last_enc_mode:
-                                         # no report of the encoder form
+                                         # no report of the encoder form; from before the conv route: the sparse route only
         fn = getattr(lib, name)          # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

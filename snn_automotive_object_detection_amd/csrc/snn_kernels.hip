@@ -73,6 +73,17 @@ struct WeightPlanesScope {
     ~WeightPlanesScope() { g_weight_planes = prev; }
 };
 
+// conv route of the RPN head forward this thread is inside (snn_rpn_head_forward_routed; every other entry: the sparse route = today's plan).
+// dense: the sparse plan is not taken (as SNN_SPARSE=0, for this call); gated (set by rpn_head_impl for an AUTO call whose plan is the sparse
+// one): the conv enqueues compress + count, the decision, and BOTH launches behind the gate word stat[2]
+struct ConvRoute { int route; float crossover; int32_t* stat; bool gated; };
+static thread_local ConvRoute g_conv_route = {SNN_ROUTE_SPARSE, 0.0f, nullptr, false};
+struct ConvRouteScope {
+    ConvRoute prev;
+    ConvRouteScope(int route, float crossover, int32_t* stat) : prev(g_conv_route) { g_conv_route = ConvRoute{route, crossover, stat, false}; }
+    ~ConvRouteScope() { g_conv_route = prev; }
+};
+
 static NeuronP make_p(const snn_params* p, float v_th) {
     NeuronP q;
     q.ca = p->dt_tau_mem; q.cb = p->neg_dt_tau_syn; q.v_leak = p->v_leak; q.v_reset = p->v_reset;
@@ -1177,7 +1188,7 @@ static bool sparse_plan(int Tc, SparsePlan* sp, long long units = 0, int n_block
 // general LIF epilogue outside the straight-line grid (round 5: T_det = 17 .. 26 and spike-rate mode used to take the all-dense launch).
 struct SparseShape { SparsePlan sp; int n_tiles, n_blocks, grid, lds, xcd_cpx, xcd_contig, epi_general; };
 static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, int Tc, SparseShape* out) {
-    if (!knobs().sparse || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
+    if (!knobs().sparse || (conv && g_conv_route.route == SNN_ROUTE_DENSE) || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
     if (conv ? (T < 5 || T > 16 || Tc != T - 1) : (T < 5 || T > SNN_MAX_STEPS || (Tc != T - 2 && Tc != T - 1))) return false;
     if (!sparse_plan(Tc, &out->sp, conv ? 0 : M, Np / 64)) return false;
     const SparsePlan& sp = out->sp;
@@ -1200,7 +1211,9 @@ static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, 
 
 // the sparse launch pair: compress the planes e_3 .., then the mixed dense / sparse contraction + LIF (conv: the RPN's shared 3x3
 // convolution; !conv: a linear layer on word-major period planes - the detector's fc6).  `side` = sparse_side_bytes() of scratch.
-// Returns 1 if the launches were enqueued (the layer is done), 0 if this configuration takes the dense launch, negative on error.
+// Returns 1 if the launches were enqueued (the layer is done), 0 if this configuration takes the dense launch, negative on error;
+// 2 on the gated conv route (g_conv_route.gated: compress + count, the decision, and this launch behind the gate - the caller enqueues the
+// dense launch behind the same gate).
 // (Every eligibility check comes before the first launch: a configuration that ends on the dense kernel enqueues nothing here.)
 // mode: SPARSE_RUN = compress + launch; SPARSE_QUERY = would it run? (nothing is enqueued); SPARSE_RUN_COMPRESSED = the caller's encoder has
 // already written the compressed planes into `side` (RPN head: encode_block, snn_encode.h)
@@ -1226,12 +1239,28 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
                       : conv ? (const void*)k_gemm_lif_sparse1<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse1<false, 2> : (const void*)k_gemm_lif_sparse1<false, 1>;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, sh.lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    const bool gated = conv && g_conv_route.gated;
+    if (gated && (mode != SPARSE_RUN || !g_conv_route.stat || a.cnt_img)) return fail(-3, "conv route: gated launch outside its plan (internal)");
     if (mode != SPARSE_RUN_COMPRESSED) {
         CompressArgs ca;
         memset(&ca, 0, sizeof(ca));
         ca.enc = a.A; ca.cmp = cmp; ca.Pe = (unsigned)Pe; ca.Cw = Kw; ca.nd = sp.nd;
-        hipLaunchKernelGGL(k_compress_planes, dim3(cdiv(Pe, 256), Kw / 2, a.Tc - sp.nd), dim3(256), 0, s, ca);
-        SNN_CHECK_LAUNCH("k_compress_planes");
+        const dim3 gc(cdiv(Pe, 256), Kw / 2, a.Tc - sp.nd);
+        if (gated) {                                  // the counting twin, then the decision: route_stat[2] is the gate word
+            // hit counters: in the side buffer's per-position spike counters (spike-rate mode only, which is never gated), a cache line apart
+            int* const slots = (int*)((char*)side + align_up((size_t)cmp_bytes, 256));
+            const size_t room = align_up((size_t)P * 4, 256) + 256;                         // (sparse_side_bytes: what lies behind the compressed planes)
+            const int nslots = (int)min((size_t)ROUTE_SLOTS_MAX, room / (ROUTE_SLOT_STRIDE * sizeof(int)));
+            if (hipMemsetAsync(slots, 0, (size_t)nslots * ROUTE_SLOT_STRIDE * sizeof(int), s) != hipSuccess) return fail(-3, "hipMemsetAsync failed");
+            hipLaunchKernelGGL(k_compress_count_planes, gc, dim3(256), 0, s, ca, slots, nslots);
+            SNN_CHECK_LAUNCH("k_compress_count_planes");
+            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_conv_route.stat, (const int*)slots, nslots,
+                               cdiv(Pe, 16) * (Kw / 2) * (a.Tc - sp.nd), g_conv_route.crossover, -1);
+            SNN_CHECK_LAUNCH("k_route_decide");
+        } else {
+            hipLaunchKernelGGL(k_compress_planes, gc, dim3(256), 0, s, ca);
+            SNN_CHECK_LAUNCH("k_compress_planes");
+        }
     }
     SparseConvArgs sa;
     memset(&sa, 0, sizeof(sa));
@@ -1248,6 +1277,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     memcpy(sa.div, a.div, sizeof(sa.div));
     memcpy(sa.lv, a.lv, sizeof(sa.lv));
     sa.xcd_cpx = sh.xcd_cpx; sa.xcd_contig = sh.xcd_contig;
+    if (gated) { sa.gate = (const int*)g_conv_route.stat + 2; sa.gate_want = 0; }
     // spike-rate mode: the LIF epilogue adds its popcounts per row (RoI: straight into the caller's counters; conv: into per-position
     // counters behind the compressed planes, summed per (level, image) by a small launch afterwards)
     uint32_t* cnt_pos = nullptr;
@@ -1266,7 +1296,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     // round 6: the FAT conv on 4 x 1 waves (T = 7 .. 9, LIF in registers) in its ping-pong form - one persistent work-group of 8 waves per CU
     // (snn_sparse_pp.h); same plan, same arguments, bit-identical planes
     const int pp_ns = a.Tc - sp.nd;
-    if (g_weight_planes == 3 && conv && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
+    if (g_weight_planes == 3 && conv && !gated && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
         const void* kpp = pp_ns == 4 ? (const void*)k_conv_lif_pp<4> : (const void*)k_conv_lif_pp<5>;
         e = hipFuncSetAttribute(kpp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -1292,7 +1322,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
         hipLaunchKernelGGL(k_sum_pos_counts, dim3(a.n_levels * a.max_n, POSCNT_CHUNKS), dim3(256), 0, s, pa);
         SNN_CHECK_LAUNCH("k_sum_pos_counts");
     }
-    return 1;
+    return gated ? 2 : 1;
 }
 
 int snn_debug_tile_shape(int conv, long long units, int k_in, int n_cols, int num_steps, int spike_rates, int layer, int32_t* out) {
@@ -1373,6 +1403,7 @@ static int conv3x3_lif_bf16x3_impl(const uint32_t* enc, size_t enc_stride, const
     if (rc < 0) return rc;
     g_last_conv_sparse = rc;
     if (rc == 1) return 0;
+    if (rc == 2) { a.gate = (const int*)g_conv_route.stat + 2; a.gate_want = 1; }      // the gated route: the dense launch on the raw period planes, behind the same word
     if (sparse_mode == SPARSE_RUN_COMPRESSED) return fail(-3, "snn_conv3x3_lif_bf16x3: the encoder wrote compressed planes but the conv takes the dense launch (internal)");
     return launch_gemm3(G3_CONV_LIF_TILE, tl.mt, wn, a, (hipStream_t)s);
 }
@@ -2026,17 +2057,25 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
     // round 5: where the conv will run the structured-sparse launch, the encoder launch writes the planes e_3 .. compressed itself (no
     // k_compress_planes launch, no raw words of those planes).  Asked of the conv's own launcher (nothing is enqueued by the query), so that
     // the two stages cannot disagree - also for a stage-by-stage caller
-    bool fold = false;
+    // conv route AUTO (snn_rpn_head_forward_routed): where the plan is the sparse one - and the call counts no spikes - the encoder leaves every
+    // period plane raw (the form the dense launch reads), and the conv stage enqueues compress + count, the decision and both launches behind the
+    // gate word; every other configuration runs its plan as it is
+    bool fold = false, route_gated = false;
     {
         NeuronP npq = make_p(p, p->v_th_enc);
         if (per) npq.v_fire = ENC_FIRED;
         const EncTh* ethq;
-        if (knobs().enc_fold && prec_family(p) == SNN_PRECISION_BF16X3 && per && wm_rows && enc_mode(npq, &ethq) == ENC_QUANT) {
+        const bool want_auto = g_conv_route.route == SNN_ROUTE_AUTO && !spike_counts && stage_mask == SNN_STAGE_ALL;
+        const bool may_fold = knobs().enc_fold && enc_mode(npq, &ethq) == ENC_QUANT;
+        if (prec_family(p) == SNN_PRECISION_BF16X3 && per && wm_rows && (may_fold || want_auto)) {
             bool split_q = split;
-            fold = conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint16_t*)w_shared_packed, spk, stride, spike_counts, max_n,
-                                           stream, true, &split_q, per, (char*)ws + o_cur, o_cnt - o_cur, SPARSE_QUERY) == 1;
+            const bool sparse_plan = conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint16_t*)w_shared_packed, spk, stride, spike_counts,
+                                                             max_n, stream, true, &split_q, per, (char*)ws + o_cur, o_cnt - o_cur, SPARSE_QUERY) == 1;
+            route_gated = sparse_plan && want_auto;
+            fold = sparse_plan && may_fold && !route_gated;
         }
     }
+    g_conv_route.gated = route_gated;
     uint32_t* enc_cmp = fold ? (uint32_t*)((char*)ws + o_cur) : nullptr;
     if (stage_mask & SNN_STAGE_ENCODE) {                        // rpn.py:101, all levels in one launch
         EncLevels el;
@@ -2063,6 +2102,7 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         SNN_CHECK_LAUNCH("k_encode_levels");
     }
     if (stage_mask & SNN_STAGE_CONV_LIF) {
+        int conv_sparse = 0;                                     // g_last_conv_sparse of this call's conv (bf16x3 family)
         if (prec_family(p) == SNN_PRECISION_F32) {
             if (spike_counts) {
                 hipError_t e = hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * n_levels * max_n, s);
@@ -2084,7 +2124,14 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
                          : conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint16_t*)w_shared_packed,
                                                    spk, stride, spike_counts, max_n, stream, wm_rows != 0, &split, per,
                                                    (char*)ws + o_cur, o_cnt - o_cur, fold ? SPARSE_RUN_COMPRESSED : SPARSE_RUN);
+            g_conv_route.gated = false;
             if (rc) return rc;
+            conv_sparse = prec_family(p) == SNN_PRECISION_BF16X3 ? g_last_conv_sparse : 0;
+        }
+        // route_stat of a call that did not decide on the device: {0, 0, 0 = the sparse launch ran (and always in spike-rate mode) / 1 = dense, 0}
+        if (g_conv_route.stat && conv_sparse != 2) {
+            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_conv_route.stat, (const int*)nullptr, 0, 0, 0.0f, (spike_counts || conv_sparse) ? 0 : 1);
+            SNN_CHECK_LAUNCH("k_route_decide");
         }
     }
     g_last_rpn_planes[0] = o_spk; g_last_rpn_planes[1] = split ? 1 : 0; g_last_rpn_planes[2] = (unsigned long long)P;
@@ -2135,6 +2182,30 @@ int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, in
                          void* ws, size_t ws_bytes, snn_stream_t stream) {
     return snn_rpn_head_forward_stages_typed(lv, SNN_FEAT_F32, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox,
                                              spike_counts, sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, stream);
+}
+
+// the routed forward's workspace: the plain forward's.  Its first plane set holds the raw planes of every period (the encoder form of the dense
+// plan), its side buffer the compressed planes; the gate word is route_stat[2], in the caller's array
+size_t snn_rpn_head_workspace_bytes_routed(const snn_rpn_level* lv, int n_levels, int C, int A, int T, int precision, int route) {
+    if (route != SNN_ROUTE_SPARSE && route != SNN_ROUTE_DENSE && route != SNN_ROUTE_AUTO) return 0;
+    return snn_rpn_head_workspace_bytes(lv, n_levels, C, A, T, precision);
+}
+
+int snn_rpn_head_forward_routed(const snn_rpn_level* lv, int fdt, int n_levels, int C, int A, int T, const snn_params* p,
+                                const void* w_shared_packed, const float* w_heads_packed, float* out_logits, float* out_bbox,
+                                unsigned long long* spike_counts, float* sum_logits, float* sum_bbox, void* ws, size_t ws_bytes,
+                                int route, float crossover, int32_t* route_stat, snn_stream_t stream) {
+    if (route != SNN_ROUTE_SPARSE && route != SNN_ROUTE_DENSE && route != SNN_ROUTE_AUTO)
+        return fail(-1, "snn_rpn_head_forward_routed: unknown route %d", route);
+    if (route == SNN_ROUTE_AUTO && !route_stat) return fail(-1, "snn_rpn_head_forward_routed: SNN_ROUTE_AUTO needs route_stat");
+    if (route == SNN_ROUTE_AUTO && crossover != crossover) return fail(-1, "snn_rpn_head_forward_routed: crossover is not a number");
+    if (lv && p && n_levels > 0 && n_levels <= SNN_MAX_LEVELS && C > 0 && T >= 1) {      // (anything else: rpn_head_impl's own message)
+        const size_t need = snn_rpn_head_workspace_bytes_routed(lv, n_levels, C, A, T, p->precision, route);
+        if (ws_bytes < need) return fail(-1, "snn_rpn_head_forward_routed: workspace %zu < %zu bytes", ws_bytes, need);
+    }
+    const ConvRouteScope scope(spike_counts ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);      // (spike-rate mode: today's plan on every route)
+    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
+                         sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, nullptr, stream, fdt);
 }
 
 int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,

@@ -91,6 +91,8 @@ struct SparseConvArgs {
     uint32_t div[SNN_MAX_STEPS];
     NeuronP p;
     ConvLevelDev lv[SNN_MAX_LEVELS];
+    const int* gate;             // conv route (CONV only; null everywhere else): as Gemm3Args.gate - the launch leaves at entry unless *gate == gate_want
+    int gate_want;
 };
 
 // Reduction-index permutation of a linear layer's period planes (the detector's fc6).  The flattened RoI features run (channel, bin):
@@ -192,6 +194,63 @@ __global__ __launch_bounds__(256) void k_compress_planes(const CompressArgs a) {
     const size_t Pe = a.Pe;
     out[0] = c4[0]; out[Pe] = c4[1]; out[2 * Pe] = c4[2];
     out[3 * Pe] = c4[3];
+}
+
+// ---- conv route (snn_rpn_head_forward_routed) ----
+// k_compress_planes' counting twin: the same four dwords per (row, step), and the density statistic the route is decided on.
+// BLOCK = 16 consecutive rows (aligned to 16 in the Pe padded rows of a word plane: a quarter of a wave here) x one 64-k step x one
+// compressed plane; HIT = a block in which some row's secondary-occupancy dword is non-zero - an M-tile on which the sparse launch's
+// centre tap issues its second pass.  One ballot per wave, one LDS add per wave with a hit, one integer atomic per work-group with a hit -
+// exact and order-independent.  The atomics go to `nslots` counters (zeroed by the launcher) a cache line apart, picked by the block index:
+// on a dense input nearly every work-group has a hit, and 27 000 atomics on ONE address cost 0.2 ms (profiles/route_crossover.txt); k_route_decide sums them.
+#define ROUTE_SLOT_STRIDE 32                        // ints between two counters: 128 bytes
+#define ROUTE_SLOTS_MAX 64
+__global__ __launch_bounds__(256) void k_compress_count_planes(const CompressArgs a, int* __restrict__ slots, const int nslots) {
+    __shared__ uint16_t code[256];
+    __shared__ int wg_hits;
+    code[threadIdx.x] = sp_byte_code(threadIdx.x);
+    if (threadIdx.x == 0) wg_hits = 0;
+    __syncthreads();
+    const unsigned int row = blockIdx.x * 256 + threadIdx.x;
+    const int w2 = blockIdx.y, ts = blockIdx.z, t = a.nd + ts;
+    uint32_t c4[4] = {0u, 0u, 0u, 0u};
+    if (row < a.Pe) {
+        sp_compress_pair(a.enc[((size_t)t * a.Cw + 2 * w2) * a.Pe + row], a.enc[((size_t)t * a.Cw + 2 * w2 + 1) * a.Pe + row], code, c4);
+        uint32_t* out = a.cmp + ((size_t)ts * (a.Cw / 2) + w2) * SP_A_ARR * a.Pe + row;
+        const size_t Pe = a.Pe;
+        out[0] = c4[0]; out[Pe] = c4[1]; out[2 * Pe] = c4[2];
+        out[3 * Pe] = c4[3];
+    }
+    const unsigned long long sec = __ballot(c4[3] != 0u);        // (rows past Pe: zero)
+    if ((threadIdx.x & 63) == 0 && sec) {
+        int n = 0;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) n += ((sec >> (16 * g)) & 0xffffull) != 0ull;
+        atomicAdd(&wg_hits, n);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_hits)
+        atomicAdd(slots + (size_t)ROUTE_SLOT_STRIDE * ((blockIdx.x + 3u * blockIdx.y + 5u * blockIdx.z) % (unsigned)nslots), wg_hits);
+}
+
+// one wave: route_stat = {hits, blocks, route, 0}.  fixed >= 0: the route the host chose ({0, 0, fixed, 0}); fixed < 0: hits = the sum of the
+// counters, and the decision - dense (1) iff hits > crossover x blocks, in fp32 as stated in snn_hip.h.  stat[2] is the gate word of the two
+// conv launches.
+__global__ __launch_bounds__(64) void k_route_decide(int* __restrict__ stat, const int* __restrict__ slots, int nslots, int blocks, float crossover, int fixed) {
+    if (blockIdx.x) return;
+    if (fixed >= 0) {
+        if (threadIdx.x == 0) { stat[0] = 0; stat[1] = 0; stat[2] = fixed; stat[3] = 0; }
+        return;
+    }
+    int hits = 0;
+    for (int i = threadIdx.x; i < nslots; i += 64) hits += slots[(size_t)ROUTE_SLOT_STRIDE * i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) hits += __shfl_xor(hits, off);
+    if (threadIdx.x == 0) {
+        stat[0] = hits; stat[1] = blocks;
+        stat[2] = (float)hits > crossover * (float)blocks ? 1 : 0;
+        stat[3] = 0;
+    }
 }
 
 // LIF over T steps of NP independent neurons per lane from the period sums in the LDS tile image: the straight-line form of

@@ -629,17 +629,36 @@ def _rpn_rates(lib, lv, n_levels: int, C_: int, A: int, T: int, max_n: int, coun
 
 def rpn_head_forward(feats: Sequence[torch.Tensor], C_: int, A: int, T: int, p: snn_params,
                      w_shared_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False,
-                     stage_mask: int = 7):
+                     stage_mask: int = 7, conv_route: Optional[str] = None, conv_crossover: Optional[float] = None,
+                     route_stat: Optional[torch.Tensor] = None):
     """Returns (out_logits [P,A], out_bbox [P,4A], level_rows, extras) — position-major outputs.
-    ``stage_mask`` (SNN_STAGE_*: 1 encode, 2 conv+LIF, 4 LI heads) is for profiling only."""
+    ``stage_mask`` (SNN_STAGE_*: 1 encode, 2 conv+LIF, 4 LI heads) is for profiling only.
+    ``conv_route`` ("sparse" / "dense" / "auto"; None: the plain entry, i.e. "sparse") goes through snn_rpn_head_forward_routed with
+    ``conv_crossover`` (None: SNN_ROUTE_DEFAULT_CROSSOVER) and ``route_stat``, a device int32[4] the call fills on the stream ("auto" needs it;
+    nothing here reads it back)."""
     lib = _lib.load()
     feats, fdt, lv, rows, max_n = _rpn_levels(feats, C_)
     dev = feats[0].device
-    ws = _WS.get(dev, lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, T, p.precision))
+    routed = conv_route is not None
+    if routed:
+        if conv_route not in _lib.CONV_ROUTES:
+            raise _lib.SnnHipError("conv_route must be one of %s, got %r" % (sorted(_lib.CONV_ROUTES), conv_route))
+        if stage_mask != 7:
+            raise _lib.SnnHipError("conv_route goes with the whole forward (stage_mask 7)")
+        if route_stat is not None and (not route_stat.is_cuda or route_stat.dtype != torch.int32 or route_stat.numel() < 4 or not route_stat.is_contiguous()):
+            raise _lib.SnnHipError("route_stat must be a contiguous int32[4] on the GPU")
+        route = _lib.CONV_ROUTES[conv_route]
+        ws_bytes = lib.snn_rpn_head_workspace_bytes_routed(lv, len(feats), C_, A, T, p.precision, route)
+    else:
+        ws_bytes = lib.snn_rpn_head_workspace_bytes(lv, len(feats), C_, A, T, p.precision)
+    ws = _WS.get(dev, ws_bytes)
     out_logits, out_bbox, (counts, sum_l, sum_b) = _rpn_outputs(sum(rows), A, len(feats), max_n, spike_rates, dev)
     tail = (C_, A, T, C.byref(p), _ptr(w_shared_packed), _ptr(w_heads_packed), _ptr(out_logits), _ptr(out_bbox),
             _ptr(counts), _ptr(sum_l), _ptr(sum_b), _ptr(ws), ws.numel(), int(stage_mask), _stream())
-    if not fdt:
+    if routed:
+        rtail = tail[:-2] + (route, float(_lib.ROUTE_DEFAULT_CROSSOVER if conv_crossover is None else conv_crossover), _ptr(route_stat), _stream())
+        _typed_call(lambda fs, d: lib.snn_rpn_head_forward_routed(_rpn_table(fs), d, len(fs), *rtail), feats, fdt, "snn_rpn_head_forward_routed")
+    elif not fdt:
         _lib.check(lib.snn_rpn_head_forward_stages(lv, len(feats), *tail), "snn_rpn_head_forward")
     else:
         _typed_call(lambda fs, d: lib.snn_rpn_head_forward_stages_typed(_rpn_table(fs), d, len(fs), *tail), feats, fdt, "snn_rpn_head_forward")

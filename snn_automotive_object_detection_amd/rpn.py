@@ -5,6 +5,7 @@ Same constructor, same ``forward`` signature and return values, same ``state_dic
 ``RegionProposalNetwork.forward`` (rpn.py:613) can call it unchanged.  The spike-rate variant the
 reference keeps in a string literal (rpn.py:126-200, enabled there by editing the source) is the
 attribute ``spike_rates`` here.  Inference only (no autograd through the kernels)."""
+import os
 import threading
 import warnings
 from typing import List, Tuple
@@ -123,9 +124,16 @@ class RPNHeadSNN(_SpikingHead):
 
     _version = 2
 
-    def __init__(self, in_channels: int, num_anchors: int, num_steps) -> None:
+    def __init__(self, in_channels: int, num_anchors: int, num_steps, conv_route=None, conv_crossover=None) -> None:
         super().__init__()
         self.num_steps = num_steps                                    # rpn.py:52
+        # launch plan of the 3x3 conv + LIF, per call (include/snn_hip.h: snn_rpn_head_forward_routed): "sparse" (the default
+        # plan), "dense", or "auto" (decided on the device from the input's density); None reads SNN_CONV_ROUTE at each forward (default
+        # "sparse").  conv_crossover: the hit rate above which "auto" takes the dense side (None: SNN_ROUTE_DEFAULT_CROSSOVER).
+        # route_stat: the last forward's device int32[4] = {hits, blocks, route taken, 0} (None on the plain "sparse" path); never read here.
+        self.conv_route = conv_route
+        self.conv_crossover = conv_crossover
+        self.route_stat = None
         self.dt = 0.001                                               # rpn.py:55
         self.p_enc = ops.LIFParameters(v_th=torch.tensor(0.25))       # rpn.py:58
         self.p_lif = ops.LIFParameters(alpha=100, v_th=torch.tensor(0.1))   # rpn.py:67
@@ -206,8 +214,16 @@ class RPNHeadSNN(_SpikingHead):
     @torch.no_grad()
     def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
         C, A, p, w_shared, w_heads = self._pass_args()
-        out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward(
-            list(x), C, A, int(self.num_steps), p, w_shared, w_heads, spike_rates=self.spike_rates)
+        route = self.conv_route if self.conv_route is not None else os.environ.get("SNN_CONV_ROUTE", "sparse")
+        if route == "sparse":                                         # the plain entry: the launches of every earlier version
+            self.route_stat = None
+            out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward(
+                list(x), C, A, int(self.num_steps), p, w_shared, w_heads, spike_rates=self.spike_rates)
+        else:
+            self.route_stat = torch.empty(4, dtype=torch.int32, device=x[0].device)
+            out_l, out_b, rows, (counts, _, _, rate_rows) = ops.rpn_head_forward(
+                list(x), C, A, int(self.num_steps), p, w_shared, w_heads, spike_rates=self.spike_rates, conv_route=route,
+                conv_crossover=self.conv_crossover, route_stat=self.route_stat)
         if self.spike_rates:
             self.last_spike_counts = counts                           # [levels, N] int64: shared-LIF spikes (tests, energy report)
         return self._level_views(x, out_l, out_b, rows, rate_rows)
