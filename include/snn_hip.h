@@ -548,6 +548,44 @@ int snn_rpn_head_forward_routed(const snn_rpn_level* levels_host, int feat_dtype
                                 float* sum_bbox, void* workspace, size_t workspace_bytes, int route, float crossover,
                                 int32_t* route_stat, snn_stream_t stream);
 
+/* ---- fc6 route of the detector head (opt-in, per call) --------------------------------
+ * fc6 + LIF has the same two launch plans for the bf16x3 family on bin-major period planes (reduction order k' = bin * C + c, w6_inner = 49):
+ * the structured-sparse one, whose cost grows with the share of 16-RoI tiles that hold a third or fourth spike of one period in a nibble,
+ * and the all-dense one.  snn_det_head_forward_routed is snn_det_head_forward_k_typed, snn_det_head_forward_roialign_routed is
+ * snn_det_head_forward_roialign_k_typed, each with the choice made per call (SNN_ROUTE_* above):
+ *   SNN_ROUTE_SPARSE  the plain entry's launches, bit for bit
+ *   SNN_ROUTE_DENSE   what a process started with SNN_SPARSE=0 runs for this call, bit for bit
+ *   SNN_ROUTE_AUTO    decided ON THE DEVICE, no host read: the encoder leaves every period plane raw (no fold; channels-last RoIAlign input:
+ *                     the raw bin-major form), k_permute_planes brings the planes into bin-major order where they are not, one launch
+ *                     compresses the planes e_3 .. and counts the HITS among the BLOCKS - block = 16 consecutive RoIs (cut every 16 rows
+ *                     from row 0; the last block is short; rows of a plane stride beyond R belong to no block) x one 64-k word pair of the
+ *                     bin-major order (D / 64 of them) x one compressed plane e_n, n = 3 .. fc6's window; hit = a block in which some row's
+ *                     secondary-occupancy dword is non-zero (some nibble of that plane holds at least three ones) -, one thread sets
+ *                     route = (float)hits > crossover * (float)blocks ? 1 : 0, then BOTH fc6 launches are enqueued on the same raw planes
+ *                     and permuted weights and the one whose route was not taken leaves at entry; fc7 and the LI heads follow as always.
+ *                     crossover <= -1 always takes the dense side, crossover >= 1 never does.
+ * route_stat (device, int32[4], written on `stream`; nullable unless AUTO) = {hits, blocks, route taken (0 sparse / 1 dense), 0}.
+ * SPARSE and DENSE count nothing: route_stat = {0, 0, 0 / 1 = the fc6 launch that ran, 0}.  Where the call's fc6 plan is dense anyway
+ * (SNN_PRECISION_F32 / F32_STRICT / MXFP6, C % 64 != 0, a non-zero rest or reset potential, a lif6 that fires at step 0, knobs), all three
+ * routes run that plan and route_stat = {0, 0, 1, 0}.  With w6_inner != 49 AUTO decides nothing and runs the plain plan (route_stat[2] says
+ * which launch that was).  In spike-rate mode (spk6_count != NULL) all three routes run the plain plan and route_stat = {0, 0, 0, 0}.
+ * The workspace is the plain forward's; the _routed size query exists so that this can change.  An unknown route, a null route_stat with
+ * AUTO and a workspace below the query's size return -1 with nothing enqueued.  The readout entries have no route.
+ * SNN_FC6_ROUTE_DEFAULT_CROSSOVER: see profiles/fc6_route_crossover.txt. */
+#define SNN_FC6_ROUTE_DEFAULT_CROSSOVER 0.061f
+size_t snn_det_head_workspace_bytes_routed(int R, int D, int Hd, int K, int K4, int T, int precision, int route);
+int snn_det_head_forward_routed(const void* x, int feat_dtype, int R, int D, int Hd, int K, int K4, int T, const snn_params* p_host,
+                                const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls,
+                                float* sum_bbox, void* workspace, size_t workspace_bytes, int route, float crossover,
+                                int32_t* route_stat, snn_stream_t stream);
+int snn_det_head_forward_roialign_routed(const snn_roi_level* levels_host, int feat_dtype, int n_levels, int C, const float* rois,
+                                         const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                         const snn_params* p_host, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                         const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                         uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* workspace, size_t workspace_bytes,
+                                         int route, float crossover, int32_t* route_stat, snn_stream_t stream);
+
 /* the two stage-level calls the tests compare planes through */
 int snn_encode_nchw_typed(const void* feat, int feat_dtype, int N, int C, int H, int W, int T, const snn_params* p_host,
                           uint32_t* planes, size_t plane_stride_words, snn_stream_t stream);

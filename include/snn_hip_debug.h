@@ -43,7 +43,7 @@ int snn_debug_last_enc_mode(void);
  * (csrc/snn_sparse.h: planes e_3 .. on v_smfmac, no dense launch), 0 if it took the dense launch (SNN_SPARSE=0, conv T outside 5 .. 16, channel counts that are not multiples of 64, ...),
  * 2 if it enqueued both behind the gate word of SNN_ROUTE_AUTO (snn_rpn_head_forward_routed: route_stat[2] says which one computed). */
 int snn_debug_last_conv_path(void);
-int snn_debug_last_fc6_path(void);      /* the same for the detector head's fc6 + LIF */
+int snn_debug_last_fc6_path(void);      /* the same for the detector head's fc6 + LIF (2: the gated pair of snn_det_head_forward_routed / _roialign_routed) */
 /* Introspection (parity tests): where the calling thread's last detector-head forward left its hidden spike planes in the caller's
  * workspace: out3[0] / out3[1] = byte offsets of lif6's / lif7's planes ([T][R][Hd/32] words; lif6's are word-major [T][Hd/32][R] if
  * out3[2] == 1).  The tests attribute every RoI that is off tolerance to a flipped spike of the launch that actually ran. */

@@ -18,6 +18,7 @@ NO_TYPED_KERNEL = 1                                       # SNN_STATUS_NO_TYPED_
 PRECISIONS = {"f32": 0, "bf16x3": 1, "mxfp6": 2, "f32_strict": 3, "bf16": 4}
 CONV_ROUTES = {"sparse": 0, "dense": 1, "auto": 2}      # SNN_ROUTE_*
 ROUTE_DEFAULT_CROSSOVER = 0.357                            # SNN_ROUTE_DEFAULT_CROSSOVER (tests/test_conv_route_cpu.py compares it with the header)
+FC6_ROUTE_DEFAULT_CROSSOVER = 0.061                         # SNN_FC6_ROUTE_DEFAULT_CROSSOVER (tests/test_fc6_route_cpu.py compares it with the header)
 
 
 class snn_params(C.Structure):
@@ -184,6 +185,13 @@ SYMBOLS = {
                                               C.POINTER(snn_params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float,
                                               C.c_void_p, c_stream]),
+    # the detector head with its fc6 route chosen per call: the typed forwards' arguments, then route, crossover, route_stat (device int32[4])
+    "snn_det_head_workspace_bytes_routed": (C.c_size_t, [C.c_int] * 8),
+    "snn_det_head_forward_routed": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +
+                                    [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_float, C.c_void_p, c_stream]),
+    "snn_det_head_forward_roialign_routed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p] + [C.c_int] * 5 + [C.POINTER(snn_params), C.c_void_p, C.c_int] +
+                                             [C.c_void_p] * 9 + [C.c_size_t, C.c_int, C.c_float, C.c_void_p, c_stream]),
     "snn_encode_nchw_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(snn_params), C.c_void_p, C.c_size_t, c_stream]),
     "snn_roi_align_encode_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),

@@ -130,12 +130,12 @@ struct Gemm3Args {
     int n_short;
     NeuronP p;
     ConvLevelDev lv[SNN_MAX_LEVELS];
-    // conv route (G3_CONV_LIF_TILE only; every other caller leaves it null): a device word written earlier on the stream; a launch whose word
-    // differs from gate_want leaves at entry, all work-groups alike (G3_GATE)
+    // conv / fc6 route (G3_CONV_LIF_TILE and fc6's G3_FC_LIF_TILE launch; every other caller leaves it null): a device word written earlier on
+    // the stream; a launch whose word differs from gate_want leaves at entry, all work-groups alike (G3_GATE)
     const int* gate;
     int gate_want;
 };
-// the gate of a conv kernel: work-group uniform (kernel arguments and one word of memory), in the kernel's entry block - ahead of every barrier and LDS-DMA
+// the gate of a conv / linear + LIF kernel: work-group uniform (kernel arguments and one word of memory), in the kernel's entry block - ahead of every barrier and LDS-DMA
 #define G3_GATE(a) do { if ((a).gate && *(a).gate != (a).gate_want) return; } while (0)
 
 // ---- spike-rate reduction fused into the LIF epilogues (rpn.py:163-172, faster_rcnn.py:556-557: the rates are spike COUNTS / (T * neurons)).
@@ -257,7 +257,7 @@ __device__ __forceinline__ void gemm_bf16x3_body(const Gemm3Args& args, const in
     // many L2s.  Tiles past the end (the grid is padded to a multiple of `classes` tiles) leave at once.
     int nb = bid % args.n_blocks;
     int mb = bid / args.n_blocks;
-    if constexpr (MODE == G3_CONV_LIF_TILE) G3_GATE(args);      // conv route: in the entry block, ahead of every barrier and LDS-DMA (snn_sparse_kernel.h says why not first)
+    if constexpr (MODE == G3_CONV_LIF_TILE || MODE == G3_FC_LIF_TILE) G3_GATE(args);      // conv / fc6 route: in the entry block, ahead of every barrier and LDS-DMA (snn_sparse_kernel.h says why not first)
     if (args.xcd_classes) {
         const int groups = 8 / args.xcd_classes, x = bid & 7, j = bid >> 3;
         nb = 2 * (x % groups) + (j & 1);

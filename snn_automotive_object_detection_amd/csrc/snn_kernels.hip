@@ -83,6 +83,14 @@ struct ConvRouteScope {
     ConvRouteScope(int route, float crossover, int32_t* stat) : prev(g_conv_route) { g_conv_route = ConvRoute{route, crossover, stat, false}; }
     ~ConvRouteScope() { g_conv_route = prev; }
 };
+// the same for fc6 + LIF of the detector head forward this thread is inside (snn_det_head_forward_routed / _roialign_routed);
+// gated is set by the head's entry for an AUTO call whose fc6 plan is the sparse launch, and cleared by det_head_from_planes
+static thread_local ConvRoute g_fc6_route = {SNN_ROUTE_SPARSE, 0.0f, nullptr, false};
+struct Fc6RouteScope {
+    ConvRoute prev;
+    Fc6RouteScope(int route, float crossover, int32_t* stat) : prev(g_fc6_route) { g_fc6_route = ConvRoute{route, crossover, stat, false}; }
+    ~Fc6RouteScope() { g_fc6_route = prev; }
+};
 
 static NeuronP make_p(const snn_params* p, float v_th) {
     NeuronP q;
@@ -1188,7 +1196,7 @@ static bool sparse_plan(int Tc, SparsePlan* sp, long long units = 0, int n_block
 // general LIF epilogue outside the straight-line grid (round 5: T_det = 17 .. 26 and spike-rate mode used to take the all-dense launch).
 struct SparseShape { SparsePlan sp; int n_tiles, n_blocks, grid, lds, xcd_cpx, xcd_contig, epi_general; };
 static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, int Tc, SparseShape* out) {
-    if (!knobs().sparse || (conv && g_conv_route.route == SNN_ROUTE_DENSE) || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
+    if (!knobs().sparse || (conv ? g_conv_route.route : g_fc6_route.route) == SNN_ROUTE_DENSE || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
     if (conv ? (T < 5 || T > 16 || Tc != T - 1) : (T < 5 || T > SNN_MAX_STEPS || (Tc != T - 2 && Tc != T - 1))) return false;
     if (!sparse_plan(Tc, &out->sp, conv ? 0 : M, Np / 64)) return false;
     const SparsePlan& sp = out->sp;
@@ -1212,8 +1220,8 @@ static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, 
 // the sparse launch pair: compress the planes e_3 .., then the mixed dense / sparse contraction + LIF (conv: the RPN's shared 3x3
 // convolution; !conv: a linear layer on word-major period planes - the detector's fc6).  `side` = sparse_side_bytes() of scratch.
 // Returns 1 if the launches were enqueued (the layer is done), 0 if this configuration takes the dense launch, negative on error;
-// 2 on the gated conv route (g_conv_route.gated: compress + count, the decision, and this launch behind the gate - the caller enqueues the
-// dense launch behind the same gate).
+// 2 on the gated conv / fc6 route (g_conv_route.gated, g_fc6_route.gated: compress + count, the decision, and this launch behind the gate -
+// the caller enqueues the dense launch behind the same gate).
 // (Every eligibility check comes before the first launch: a configuration that ends on the dense kernel enqueues nothing here.)
 // mode: SPARSE_RUN = compress + launch; SPARSE_QUERY = would it run? (nothing is enqueued); SPARSE_RUN_COMPRESSED = the caller's encoder has
 // already written the compressed planes into `side` (RPN head: encode_block, snn_encode.h)
@@ -1239,8 +1247,9 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
                       : conv ? (const void*)k_gemm_lif_sparse1<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse1<false, 2> : (const void*)k_gemm_lif_sparse1<false, 1>;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, sh.lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    const bool gated = conv && g_conv_route.gated;
-    if (gated && (mode != SPARSE_RUN || !g_conv_route.stat || a.cnt_img)) return fail(-3, "conv route: gated launch outside its plan (internal)");
+    const ConvRoute& rt = conv ? g_conv_route : g_fc6_route;
+    const bool gated = rt.gated;
+    if (gated && (mode != SPARSE_RUN || !rt.stat || a.cnt_img || a.cnt_row)) return fail(-3, "conv / fc6 route: gated launch outside its plan (internal)");
     if (mode != SPARSE_RUN_COMPRESSED) {
         CompressArgs ca;
         memset(&ca, 0, sizeof(ca));
@@ -1252,10 +1261,12 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
             const size_t room = align_up((size_t)P * 4, 256) + 256;                         // (sparse_side_bytes: what lies behind the compressed planes)
             const int nslots = (int)min((size_t)ROUTE_SLOTS_MAX, room / (ROUTE_SLOT_STRIDE * sizeof(int)));
             if (hipMemsetAsync(slots, 0, (size_t)nslots * ROUTE_SLOT_STRIDE * sizeof(int), s) != hipSuccess) return fail(-3, "hipMemsetAsync failed");
-            hipLaunchKernelGGL(k_compress_count_planes, gc, dim3(256), 0, s, ca, slots, nslots);
+            // rows that count: the conv's padded row space; a linear layer's M rows (fc6: the RoIs - rows of a wider plane stride belong to no block)
+            const long long n_rows = conv ? Pe : min(P, Pe);
+            hipLaunchKernelGGL(k_compress_count_planes, gc, dim3(256), 0, s, ca, slots, nslots, (unsigned int)n_rows);
             SNN_CHECK_LAUNCH("k_compress_count_planes");
-            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_conv_route.stat, (const int*)slots, nslots,
-                               cdiv(Pe, 16) * (Kw / 2) * (a.Tc - sp.nd), g_conv_route.crossover, -1);
+            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)rt.stat, (const int*)slots, nslots,
+                               (int)(cdiv(n_rows, 16) * (Kw / 2) * (a.Tc - sp.nd)), rt.crossover, -1);
             SNN_CHECK_LAUNCH("k_route_decide");
         } else {
             hipLaunchKernelGGL(k_compress_planes, gc, dim3(256), 0, s, ca);
@@ -1277,7 +1288,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     memcpy(sa.div, a.div, sizeof(sa.div));
     memcpy(sa.lv, a.lv, sizeof(sa.lv));
     sa.xcd_cpx = sh.xcd_cpx; sa.xcd_contig = sh.xcd_contig;
-    if (gated) { sa.gate = (const int*)g_conv_route.stat + 2; sa.gate_want = 0; }
+    if (gated) { sa.gate = (const int*)rt.stat + 2; sa.gate_want = 0; }
     // spike-rate mode: the LIF epilogue adds its popcounts per row (RoI: straight into the caller's counters; conv: into per-position
     // counters behind the compressed planes, summed per (level, image) by a small launch afterwards)
     uint32_t* cnt_pos = nullptr;
@@ -2596,21 +2607,36 @@ static int det_plan(const char* who, int R, int D, int Hd, int T, int w6_inner, 
     return 0;
 }
 
-// rounds 5 / 6: where fc6 will run the structured-sparse launch on bin-major planes, ONE encoder launch writes them - permuted, e_3 ..
-// compressed - instead of encoder + k_permute_planes + k_compress_planes.  fc6's own launcher is asked (nothing is enqueued).  feed_ok:
-// the feed's own conditions; *np, *eth: the folded encoder's neuron and threshold table
-static bool det_fc6_folds(bool feed_ok, const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
-                          uint32_t* spk6_count, void* ws, snn_stream_t stream, NeuronP* np, const EncTh** eth) {
-    if (!knobs().enc_fold || !feed_ok || w6_inner != 49 || !dp.wm || !dp.per) return false;
-    *np = make_p(p, p->v_th_enc);
-    np->v_fire = ENC_FIRED;
-    if (!enc_zero_rest(*np) || enc_mode(*np, eth) != ENC_QUANT) return false;
+// will fc6 run the structured-sparse launch on the word-major period planes at o_enc?  fc6's own launcher is asked (nothing is enqueued)
+static bool det_fc6_sparse_plan(const DetPlan& dp, int R, int D, int Hd, int T, const snn_params* p, const void* w6_packed, uint32_t* spk6_count,
+                                void* ws, snn_stream_t stream) {
     Gemm3Args a6;
     G3Tile t6;
     return spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)ws + dp.o_enc), T, R, D, Hd, p, (const uint16_t*)w6_packed,
                                       (uint32_t*)((char*)ws + dp.o_s6), (size_t)R * cdiv(Hd, 32), spk6_count, true, true, &dp.win.fc6, true,
                                       &a6, &t6) == 0 &&
            gemm3_lif_sparse(a6, false, (char*)ws + dp.o_cur, dp.o_s6 - dp.o_cur, (hipStream_t)stream, SPARSE_QUERY) == 1;
+}
+
+// rounds 5 / 6: where fc6 will run the structured-sparse launch on bin-major planes, ONE encoder launch writes them - permuted, e_3 ..
+// compressed - instead of encoder + k_permute_planes + k_compress_planes.  fc6's own launcher is asked (nothing is enqueued).  feed_ok:
+// the feed's own conditions; *np, *eth: the folded encoder's neuron and threshold table
+static bool det_fc6_folds(bool feed_ok, const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
+                          uint32_t* spk6_count, void* ws, snn_stream_t stream, NeuronP* np, const EncTh** eth) {
+    if (g_fc6_route.gated || !knobs().enc_fold || !feed_ok || w6_inner != 49 || !dp.wm || !dp.per) return false;      // (the gated fc6 route reads raw planes)
+    *np = make_p(p, p->v_th_enc);
+    np->v_fire = ENC_FIRED;
+    if (!enc_zero_rest(*np) || enc_mode(*np, eth) != ENC_QUANT) return false;
+    return det_fc6_sparse_plan(dp, R, D, Hd, T, p, w6_packed, spk6_count, ws, stream);
+}
+
+// fc6 route AUTO (snn_det_head_forward_routed): does this call enqueue compress + count, the decision and both fc6 launches
+// behind the gate word?  Where fc6's plan is the sparse launch on bin-major period planes and the call counts no spikes and reads out once;
+// every other configuration runs its plan as it is.  The encoder then leaves every period plane raw (no fold)
+static bool det_fc6_gated(const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
+                          uint32_t* spk6_count, void* ws, snn_stream_t stream, const DetReadouts* ro) {
+    if (g_fc6_route.route != SNN_ROUTE_AUTO || !g_fc6_route.stat || spk6_count || ro || w6_inner != 49 || !dp.wm || !dp.per) return false;
+    return det_fc6_sparse_plan(dp, R, D, Hd, T, p, w6_packed, spk6_count, ws, stream);
 }
 
 // the LI heads at the end of a detector pass: one readout at T (the plain forward), or the readout set with its spike counts
@@ -2626,6 +2652,15 @@ static int det_heads_tail(const uint32_t* s6, const uint32_t* s7, int R, int Hd,
     SNN_CHECK_LAUNCH("k_count_rows_ro");
     hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, s7, (unsigned long long)R * Hw, R, Hw, 0, st, ro->c7);
     SNN_CHECK_LAUNCH("k_count_rows_ro");
+    return 0;
+}
+
+// route_stat of a routed detector call that did not decide on the device: {0, 0, 0 = the sparse fc6 launch ran (and always in spike-rate
+// mode) / 1 = dense, 0}; nothing on every other entry
+static int fc6_route_fixed(int route_taken, hipStream_t s) {
+    if (!g_fc6_route.stat) return 0;
+    hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_fc6_route.stat, (const int*)nullptr, 0, 0, 0.0f, route_taken);
+    SNN_CHECK_LAUNCH("k_route_decide");
     return 0;
 }
 
@@ -2670,6 +2705,7 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
             return fail(-4, "snn_det_head_forward: the mxfp6 kernels need D, Hd %% 128 == 0");
         // (spike-rate mode: per-RoI counts come out of the LIF epilogues)
         if (!mx_tile_ok(win.fc6.n) || !mx_tile_ok(win.fc7.n)) return fail(-4, "snn_det_head_forward: T=%d does not fit a 512-row tile of the mxfp6 kernels", T);
+        if ((rc = fc6_route_fixed(spk6_count ? 0 : 1, s))) return rc;
         if ((rc = spike_gemm_lif_mx_impl(enc, T, R, D, Hd, p, (const uint32_t*)w6_packed, s6, (size_t)R * Hw, spk6_count, stream, &win.fc6))) return rc;
         if ((rc = spike_gemm_lif_mx_impl(s6, T, R, Hd, Hd, p, (const uint32_t*)w7_packed, s7, (size_t)R * Hw, spk7_count, stream, &win.fc7))) return rc;
         return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, false, ro, stream);
@@ -2689,14 +2725,20 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
         // round 4: fc6's sparse period planes e_3 .. on the structured-sparse matrix-core instruction (snn_sparse.h); its side buffers
         // live in the currents region of the workspace, which the fused layers never write
         rc = gemm3_lif_sparse(a6, false, (char*)ws + o_cur, o_s6 - o_cur, s, folded ? SPARSE_RUN_COMPRESSED : SPARSE_RUN);
+        const bool was_gated = g_fc6_route.gated;
+        g_fc6_route.gated = false;
         if (rc < 0) return rc;
         if (folded && rc != 1) return fail(-3, "snn_det_head_forward: the encoder wrote compressed planes but fc6 takes the dense launch (internal)");
+        if (was_gated && rc != 2) return fail(-3, "snn_det_head_forward: fc6 route: the gated pair was planned but fc6 did not enqueue it (internal)");
         g_last_fc_sparse = rc;
-        if (rc == 0 && (rc = launch_gemm3(G3_FC_LIF_TILE, t6.mt, wn, a6, s))) return rc;
+        if (rc == 2) { a6.gate = (const int*)g_fc6_route.stat + 2; a6.gate_want = 1; }      // the gated route: the dense launch on the same raw planes and weights, behind the same word
+        else if ((rc = fc6_route_fixed((spk6_count || rc == 1) ? 0 : 1, s))) return rc;
+        if (g_last_fc_sparse != 1 && (rc = launch_gemm3(G3_FC_LIF_TILE, t6.mt, wn, a6, s))) return rc;
         if ((rc = launch_gemm3(G3_FC_LIF_TILE, t7.mt, wn, a7, s))) return rc;
         return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, enc_wm, ro, stream);
     }
     // fc6 for all (live) time steps at once: rows m = (t - t0)*R + r   (faster_rcnn.py:498)
+    if ((rc = fc6_route_fixed(spk6_count ? 0 : 1, s))) return rc;
     const uint32_t* a6 = enc + (size_t)win.fc6.t0 * R * cdiv(D, 32);
     rc = b3 ? snn_spike_gemm_bf16x3(a6, win.fc6.n * R, D, Hd, (const uint16_t*)w6_packed, cur, Hp, stream)
             : snn_spike_gemm(a6, win.fc6.n * R, D, Hd, (const float*)w6_packed, cur, Hp, stream);
@@ -2727,6 +2769,7 @@ static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, i
     if (w6_inner > 1 && !dp.wm) return fail(-4, "snn_det_head_forward: permuted fc6 weights need the word-major fused bf16x3 path (D %% 32 == 0, x 16-byte aligned)");
     NeuronP np;
     const EncTh* eth_f = nullptr;
+    g_fc6_route.gated = det_fc6_gated(dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, ro);      // (the entry's scope clears it on every early return)
     const bool fold = det_fc6_folds(D % (49 * 64) == 0, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
     if (fold) {
         const int Te = dp.win.enc_steps, C = D / 49;
@@ -2783,6 +2826,7 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
     const bool feed_ok = feed_geo && dp.win.enc_steps <= 12;
     NeuronP np;
     const EncTh* eth_f = nullptr;
+    g_fc6_route.gated = det_fc6_gated(dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, ro);      // (the entry's scope clears it on every early return)
     const bool fold = det_fc6_folds(feed_ok, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
     // channels-last maps (SNN_FEAT_NHWC): one kernel, for the plans in which fc6 reads bin-major period planes - folded as above, or (longer windows,
     // a dense fc6) every plane raw in bin-major order where k_permute_planes would have put it, k_compress_planes following as before
@@ -2923,6 +2967,54 @@ int snn_det_head_forward_roialign_readouts_typed(const snn_roi_level* levels_hos
     return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
                                           w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
                                           ws_bytes, stream, &ro);
+}
+
+// ---- fc6 route of the detector head ----
+// the routed forward's workspace: the plain forward's.  Its front region holds the raw bin-major planes of every period, the currents region the
+// compressed planes and the hit counters; the gate word is route_stat[2], in the caller's array
+static bool route_known(int route) { return route == SNN_ROUTE_SPARSE || route == SNN_ROUTE_DENSE || route == SNN_ROUTE_AUTO; }
+size_t snn_det_head_workspace_bytes_routed(int R, int D, int Hd, int K, int K4, int T, int precision, int route) {
+    if (!route_known(route)) return 0;
+    return snn_det_head_workspace_bytes(R, D, Hd, K, K4, T, precision);
+}
+
+// the checks the two routed entries share, before anything is asked of the plan or enqueued
+static int det_route_check(const char* who, int R, int D, int Hd, int K, int K4, int T, const snn_params* p, size_t ws_bytes, int route,
+                           float crossover, const int32_t* route_stat) {
+    if (!route_known(route)) return fail(-1, "%s: unknown route %d", who, route);
+    if (route == SNN_ROUTE_AUTO && !route_stat) return fail(-1, "%s: SNN_ROUTE_AUTO needs route_stat", who);
+    if (route == SNN_ROUTE_AUTO && crossover != crossover) return fail(-1, "%s: crossover is not a number", who);
+    if (p && R > 0 && D > 0 && Hd > 0 && T >= 1) {              // (anything else: the forward's own message)
+        const size_t need = snn_det_head_workspace_bytes_routed(R, D, Hd, K, K4, T, p->precision, route);
+        if (ws_bytes < need) return fail(-1, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    }
+    return 0;
+}
+
+int snn_det_head_forward_routed(const void* x, int fdt, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
+                                const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
+                                float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
+                                float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, int route, float crossover,
+                                int32_t* route_stat, snn_stream_t stream) {
+    if (det_route_check("snn_det_head_forward_routed", R, D, Hd, K, K4, T, p, ws_bytes, route, crossover, route_stat)) return -1;
+    const Fc6RouteScope scope(spk6_count ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);      // (spike-rate mode: the plain plan on every route)
+    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
+                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+}
+
+int snn_det_head_forward_roialign_routed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
+                                         const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
+                                         const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
+                                         const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                                         uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
+                                         int route, float crossover, int32_t* route_stat, snn_stream_t stream) {
+    if (det_route_check("snn_det_head_forward_roialign_routed", R, C > 0 && C < (1 << 24) ? C * 49 : 0, Hd, K, K4, T, p, ws_bytes, route, crossover,
+                        route_stat))
+        return -1;
+    const Fc6RouteScope scope(spk6_count ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);
+    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
+                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
+                                          ws_bytes, stream, nullptr);
 }
 
 int snn_det_exchange_payload(const float* class_logits, const float* box_regression, int N, int rois_per_image, int K,

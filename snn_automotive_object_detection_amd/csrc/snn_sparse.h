@@ -91,7 +91,7 @@ struct SparseConvArgs {
     uint32_t div[SNN_MAX_STEPS];
     NeuronP p;
     ConvLevelDev lv[SNN_MAX_LEVELS];
-    const int* gate;             // conv route (CONV only; null everywhere else): as Gemm3Args.gate - the launch leaves at entry unless *gate == gate_want
+    const int* gate;             // conv route, fc6 route (null everywhere else): as Gemm3Args.gate - the launch leaves at entry unless *gate == gate_want
     int gate_want;
 };
 
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void k_compress_planes(const CompressArgs a) {
 // on a dense input nearly every work-group has a hit, and 27 000 atomics on ONE address cost 0.2 ms (profiles/route_crossover.txt); k_route_decide sums them.
 #define ROUTE_SLOT_STRIDE 32                        // ints between two counters: 128 bytes
 #define ROUTE_SLOTS_MAX 64
-__global__ __launch_bounds__(256) void k_compress_count_planes(const CompressArgs a, int* __restrict__ slots, const int nslots) {
+__global__ __launch_bounds__(256) void k_compress_count_planes(const CompressArgs a, int* __restrict__ slots, const int nslots, const unsigned int n_rows) {
     __shared__ uint16_t code[256];
     __shared__ int wg_hits;
     code[threadIdx.x] = sp_byte_code(threadIdx.x);
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void k_compress_count_planes(const CompressArg
         out[0] = c4[0]; out[Pe] = c4[1]; out[2 * Pe] = c4[2];
         out[3 * Pe] = c4[3];
     }
-    const unsigned long long sec = __ballot(c4[3] != 0u);        // (rows past Pe: zero)
+    const unsigned long long sec = __ballot(c4[3] != 0u && row < n_rows);        // (rows past Pe: zero; n_rows <= Pe: rows past it belong to no block)
     if ((threadIdx.x & 63) == 0 && sec) {
         int n = 0;
 #pragma unroll

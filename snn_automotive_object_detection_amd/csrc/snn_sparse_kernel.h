@@ -40,9 +40,9 @@ __global__ __launch_bounds__(FAT ? 256 : 512, FAT ? 2 : 4) void SP_KERNEL(const 
     // (xcd_contig == 0 - the linear layers: plain order, column block fastest: an XCD only ever sees two weight panels, and all
     // work-groups of a panel walk K together)
     int nb = blockIdx.x % args.n_blocks, mb = blockIdx.x / args.n_blocks;
-    // conv route: in the entry block, so that the gate's kernel arguments arrive with n_blocks / xcd_contig (as the kernel's very first statement the
-    // test put one more kernarg round trip in front of every work-group: 0.2 % of the step over the launch's 24 rounds of work-groups)
-    if constexpr (CONV) G3_GATE(args);
+    // conv / fc6 route: in the entry block, so that the gate's kernel arguments arrive with n_blocks / xcd_contig (as the kernel's very first statement the
+    // test put one more kernarg round trip in front of every work-group: 0.2 % of the step over the conv launch's 24 rounds of work-groups)
+    G3_GATE(args);
     if (args.xcd_contig) {
         const int x = blockIdx.x & 7, j = blockIdx.x >> 3, cpx = args.xcd_cpx, groups = args.n_blocks / cpx;
         nb = (x % groups) * cpx + j % cpx;

@@ -23,11 +23,20 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         num_classes (int): number of output classes (including background)
         num_steps (int): simulation time steps (T_det)
         only_one_bbox (bool): 4 box outputs instead of 4 per class
+        fc6_route, fc6_crossover: launch plan of fc6 + LIF per call (not in the reference; see __init__)
     """
 
-    def __init__(self, in_channels, representation_size, num_classes, num_steps, only_one_bbox=False):
+    def __init__(self, in_channels, representation_size, num_classes, num_steps, only_one_bbox=False, fc6_route=None, fc6_crossover=None):
         super().__init__()
         self.num_steps = num_steps                                     # faster_rcnn.py:433
+        # launch plan of fc6 + LIF, per call (include/snn_hip.h: snn_det_head_forward_routed; DESIGN.md 4.10): "sparse" (the default plan),
+        # "dense", or "auto" (decided on the device from the density of the RoI features' period planes); None reads SNN_FC6_ROUTE at each
+        # forward (default "sparse").  fc6_crossover: the hit rate above which "auto" takes the dense side (None:
+        # SNN_FC6_ROUTE_DEFAULT_CROSSOVER).  route_stat: the last forward's device int32[4] = {hits, blocks, route taken, 0} (None on the
+        # plain "sparse" path); never read here.  The readout methods keep the plain plan.
+        self.fc6_route = fc6_route
+        self.fc6_crossover = fc6_crossover
+        self.route_stat = None
         self.dt = 0.001                                                # :436
         self.in_channels = in_channels
         self.representation_size = representation_size
@@ -104,10 +113,20 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         return dict(Hd=self.representation_size, K=self.num_classes, K4=self.bbox_pred.weight.shape[0], p=self._params(prec),
                     w6_packed=w6, w7_packed=w7, w_heads_packed=wh, spike_rates=self.spike_rates, w6_inner=self.fc6_inner(prec))
 
+    def _route_args(self, dev) -> dict:
+        """the fc6 route of this forward: nothing on "sparse" (the plain entry: the launches of every earlier version), else the keywords
+        of the routed entry with a fresh route_stat"""
+        route = self.fc6_route if self.fc6_route is not None else os.environ.get("SNN_FC6_ROUTE", "sparse")
+        if route == "sparse":
+            self.route_stat = None
+            return {}
+        self.route_stat = torch.empty(4, dtype=torch.int32, device=dev)
+        return dict(fc6_route=route, fc6_crossover=self.fc6_crossover, route_stat=self.route_stat)
+
     @torch.no_grad()
     def forward(self, x):
         x = x.flatten(start_dim=1)                                     # :473
-        out = ops.det_head_forward(x, T=int(self.num_steps), **self._pass_args(x.shape[1], "%d" % x.shape[1]))
+        out = ops.det_head_forward(x, T=int(self.num_steps), **self._pass_args(x.shape[1], "%d" % x.shape[1]), **self._route_args(x.device))
         return self._finish(out)
 
     @torch.no_grad()
@@ -118,7 +137,8 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         if roi_batch is None:
             rois, roi_batch = rois[:, 1:5], rois[:, 0]
         out = ops.det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, T=int(self.num_steps),
-                                            **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]))
+                                            **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]),
+                                            **self._route_args(rois.device))
         return self._finish(out)
 
     @torch.no_grad()

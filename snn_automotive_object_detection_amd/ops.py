@@ -692,13 +692,35 @@ def _det_ws(lib, dev, R: int, D: int, Hd: int, K: int, K4: int, T: int, p: snn_p
     return _WS.get(dev, lib.snn_det_head_workspace_bytes(R, D, Hd, K, K4, T, p.precision))
 
 
+def _fc6_route_args(fc6_route: str, fc6_crossover: Optional[float], route_stat: Optional[torch.Tensor]):
+    """checked (route code, crossover) of a routed detector call (include/snn_hip.h: snn_det_head_forward_routed)"""
+    if fc6_route not in _lib.CONV_ROUTES:
+        raise _lib.SnnHipError("fc6_route must be one of %s, got %r" % (sorted(_lib.CONV_ROUTES), fc6_route))
+    if route_stat is not None and (not route_stat.is_cuda or route_stat.dtype != torch.int32 or route_stat.numel() < 4 or not route_stat.is_contiguous()):
+        raise _lib.SnnHipError("route_stat must be a contiguous int32[4] on the GPU")
+    return _lib.CONV_ROUTES[fc6_route], float(_lib.FC6_ROUTE_DEFAULT_CROSSOVER if fc6_crossover is None else fc6_crossover)
+
+
 def det_head_forward(x: torch.Tensor, Hd: int, K: int, K4: int, T: int, p: snn_params, w6_packed: torch.Tensor,
-                     w7_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False, w6_inner: int = 0):
+                     w7_packed: torch.Tensor, w_heads_packed: torch.Tensor, spike_rates: bool = False, w6_inner: int = 0,
+                     fc6_route: Optional[str] = None, fc6_crossover: Optional[float] = None, route_stat: Optional[torch.Tensor] = None):
+    """``fc6_route`` ("sparse" / "dense" / "auto"; None: the plain entry, i.e. "sparse") goes through snn_det_head_forward_routed with
+    ``fc6_crossover`` (None: SNN_FC6_ROUTE_DEFAULT_CROSSOVER) and ``route_stat``, a device int32[4] the call fills on the stream ("auto" needs
+    it; nothing here reads it back)."""
     lib = _lib.load()
     x = _det_rows(x)
     R, D = x.shape
     out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, x.device)
-    if R:
+    if fc6_route is not None:
+        route, crossover = _fc6_route_args(fc6_route, fc6_crossover, route_stat)
+        if R:
+            ws = _WS.get(x.device, lib.snn_det_head_workspace_bytes_routed(R, D, Hd, K, K4, T, p.precision, route))
+            rtail = (R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls),
+                     _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), route, crossover, _ptr(route_stat), _stream())
+            _typed_call(lambda xs, d: lib.snn_det_head_forward_routed(_ptr(xs[0]), d, *rtail), [x], _HALF.get(x.dtype, 0), "snn_det_head_forward_routed")
+        elif route_stat is not None:
+            route_stat.zero_()                                     # (no RoIs: nothing was counted and no launch ran)
+    elif R:
         ws = _det_ws(lib, x.device, R, D, Hd, K, K4, T, p)
         tail = (R, D, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner), _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls),
                 _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
@@ -755,12 +777,26 @@ def roi_align_encode(feats, scales, rois: torch.Tensor, roi_batch: torch.Tensor,
 
 
 def det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, Hd: int, K: int, K4: int, T: int, p: snn_params,
-                              w6_packed, w7_packed, w_heads_packed, spike_rates: bool = False, w6_inner: int = 0):
+                              w6_packed, w7_packed, w_heads_packed, spike_rates: bool = False, w6_inner: int = 0,
+                              fc6_route: Optional[str] = None, fc6_crossover: Optional[float] = None,
+                              route_stat: Optional[torch.Tensor] = None):
+    """``fc6_route``, ``fc6_crossover``, ``route_stat``: as det_head_forward (snn_det_head_forward_roialign_routed)"""
     lib = _lib.load()
     table, keep, fdt, Cc, rois, roi_batch, roi_level = _roi_feed(feats, scales, rois, roi_batch, roi_level)
     R = rois.shape[0]
     out_cls, out_bbox, extras = _det_outputs(R, K, K4, spike_rates, rois.device)
-    if R:
+    if fc6_route is not None:
+        route, crossover = _fc6_route_args(fc6_route, fc6_crossover, route_stat)
+        if R:
+            ws = _WS.get(rois.device, lib.snn_det_head_workspace_bytes_routed(R, Cc * 49, Hd, K, K4, T, p.precision, route))
+            rtail = (Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner),
+                     _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(),
+                     route, crossover, _ptr(route_stat), _stream())
+            _typed_call(lambda fs, d: lib.snn_det_head_forward_roialign_routed(table(fs), d, len(fs), *rtail), keep, fdt,
+                        "snn_det_head_forward_roialign_routed")
+        elif route_stat is not None:
+            route_stat.zero_()
+    elif R:
         ws = _det_ws(lib, rois.device, R, Cc * 49, Hd, K, K4, T, p)
         tail = (Cc, _ptr(rois), _ptr(roi_batch), _ptr(roi_level), R, Hd, K, K4, T, C.byref(p), _ptr(w6_packed), int(w6_inner),
                 _ptr(w7_packed), _ptr(w_heads_packed), _ptr(out_cls), _ptr(out_bbox), *map(_ptr, extras), _ptr(ws), ws.numel(), _stream())
