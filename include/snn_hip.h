@@ -24,6 +24,10 @@
  *   - re-entrant: no global mutable state besides the thread-local error string.  Two kinds of process-wide constants are
  *     cached at first use: the debug / A-B knobs (environment variables SNN_*, read ONCE and frozen; snn_debug_reload_knobs()
  *     re-reads them - test hook, not for concurrent use) and properties of the device (CU count, occupancy of a kernel).
+ *   - workspaces: a call that takes one is sized by its snn_*_workspace_bytes query, writes nothing behind that many bytes, and
+ *     returns the same bits whatever the bytes held before (opaque scratch; nothing is kept in it from call to call).  A workspace
+ *     below the query's size is refused (negative return, nothing enqueued) - also where this call's own layout would need less
+ *     (snn_rpn_proposals: the query bounds every level split).  tests/test_gpu_ws_state.py pins all three.
  *
  * Spike tensors never exist as fp32.  A spike train is a set of BIT-PLANES
  *     plane[t][row][w]   (uint32, bit b of word w = spike of channel 32*w+b at time step t)

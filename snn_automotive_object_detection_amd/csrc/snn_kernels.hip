@@ -2338,7 +2338,10 @@ int snn_rpn_proposals(const snn_rpn_post_level* lv, int n_levels, int N, int A, 
         kmax = max(kmax, L.k);
     }
     size_t off[13];
-    if (ws_bytes < rpn_post_layout(N, K, mask_words, off)) return fail(-2, "snn_rpn_proposals: workspace too small");
+    // (the size query does not know the level split and bounds every one of them; the call holds the caller to the query, as every other entry
+    // does, and not to the smaller layout of this split - which a caller cannot ask for)
+    if (ws_bytes < snn_rpn_proposals_workspace_bytes(N, K) || ws_bytes < rpn_post_layout(N, K, mask_words, off))
+        return fail(-2, "snn_rpn_proposals: workspace too small");
     for (int i = 0; i < N; ++i) { a.img_h[i] = image_hw_host[2 * i]; a.img_w[i] = image_hw_host[2 * i + 1]; }
     a.n_levels = n_levels; a.N = N; a.A = A; a.Ktot = K; a.post_n = post_nms_top_n;
     a.score_thresh = score_thresh; a.min_size = min_size; a.clip = (float)4.135166556742356;     // log(1000/16), boxes.py
