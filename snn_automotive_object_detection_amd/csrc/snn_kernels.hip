@@ -64,33 +64,29 @@ static inline int prec_family(int precision) {
     return precision == SNN_PRECISION_F32_STRICT ? SNN_PRECISION_F32 : precision == SNN_PRECISION_BF16 ? SNN_PRECISION_BF16X3 : precision;
 }
 static inline int prec_family(const snn_params* p) { return prec_family(p->precision); }
-// weight planes of the bf16 matrix-core launches enqueued by this thread: 3, or 1 inside a head forward at SNN_PRECISION_BF16 (the stage-level
-// entry points always run three)
-static thread_local int g_weight_planes = 3;
-struct WeightPlanesScope {
-    int prev;
-    explicit WeightPlanesScope(const snn_params* p) : prev(g_weight_planes) { g_weight_planes = (p && p->precision == SNN_PRECISION_BF16) ? 1 : 3; }
-    ~WeightPlanesScope() { g_weight_planes = prev; }
-};
+// weight planes of a bf16 matrix-core launch: 3, or 1 inside a head pass at SNN_PRECISION_BF16 (the stage-level entry points always run three)
+static inline int weight_planes(const snn_params* p) { return p->precision == SNN_PRECISION_BF16 ? 1 : 3; }
 
-// conv route of the RPN head forward this thread is inside (snn_rpn_head_forward_routed; every other entry: the sparse route = today's plan).
-// dense: the sparse plan is not taken (as SNN_SPARSE=0, for this call); gated (set by rpn_head_impl for an AUTO call whose plan is the sparse
-// one): the conv enqueues compress + count, the decision, and BOTH launches behind the gate word stat[2]
-struct ConvRoute { int route; float crossover; int32_t* stat; bool gated; };
-static thread_local ConvRoute g_conv_route = {SNN_ROUTE_SPARSE, 0.0f, nullptr, false};
-struct ConvRouteScope {
-    ConvRoute prev;
-    ConvRouteScope(int route, float crossover, int32_t* stat) : prev(g_conv_route) { g_conv_route = ConvRoute{route, crossover, stat, false}; }
-    ~ConvRouteScope() { g_conv_route = prev; }
-};
-// the same for fc6 + LIF of the detector head forward this thread is inside (snn_det_head_forward_routed / _roialign_routed);
-// gated is set by the head's entry for an AUTO call whose fc6 plan is the sparse launch, and cleared by det_head_from_planes
-static thread_local ConvRoute g_fc6_route = {SNN_ROUTE_SPARSE, 0.0f, nullptr, false};
-struct Fc6RouteScope {
-    ConvRoute prev;
-    Fc6RouteScope(int route, float crossover, int32_t* stat) : prev(g_fc6_route) { g_fc6_route = ConvRoute{route, crossover, stat, false}; }
-    ~Fc6RouteScope() { g_fc6_route = prev; }
-};
+// route of a head pass's sparse-capable layer - the RPN's conv (snn_rpn_head_forward_routed) or the detector's fc6
+// (snn_det_head_forward_routed / _roialign_routed, 4.10); every other entry and the stage-level ones: SPARSE_ROUTE = the plain plan.
+// dense: the sparse plan is not taken (as SNN_SPARSE=0, for this call); gated (decided by the pass's plan for an AUTO call whose plan is the
+// sparse one): the layer enqueues compress + count, the decision, and BOTH launches behind the gate word stat[2]
+struct SparseRoute { int route; float crossover; int32_t* stat; bool gated; };
+static const SparseRoute SPARSE_ROUTE = {SNN_ROUTE_SPARSE, 0.0f, nullptr, false};
+static bool route_known(int route) { return route == SNN_ROUTE_SPARSE || route == SNN_ROUTE_DENSE || route == SNN_ROUTE_AUTO; }
+// what a routed entry hands its pass: the caller's route - in spike-rate mode the plain plan on every route (route_stat is still written)
+static SparseRoute routed(int route, float crossover, int32_t* route_stat, bool spike_rates) {
+    return SparseRoute{spike_rates ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat, false};
+}
+// the checks the three routed entries share, before anything is asked of the plan or enqueued.  need: the routed size query's answer for
+// the call's shape; 0 where the shape is none it knows - the pass's own message follows
+static int route_check(const char* who, int route, float crossover, const int32_t* route_stat, size_t ws_bytes, size_t need) {
+    if (!route_known(route)) return fail(-1, "%s: unknown route %d", who, route);
+    if (route == SNN_ROUTE_AUTO && !route_stat) return fail(-1, "%s: SNN_ROUTE_AUTO needs route_stat", who);
+    if (route == SNN_ROUTE_AUTO && crossover != crossover) return fail(-1, "%s: crossover is not a number", who);
+    if (ws_bytes < need) return fail(-1, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return 0;
+}
 
 static NeuronP make_p(const snn_params* p, float v_th) {
     NeuronP q;
@@ -430,8 +426,8 @@ static int g3_wn(bool conv = false) { (void)conv; return knobs().bf16x3_wn ? kno
 static int g3_bm(int wn, int mt) { return mt == 8 ? 256 : G3_BM(wn, mt); }
 
 template <int MODE>
-static const void* g3_kernel(int mt, int wn) {
-    if (g_weight_planes == 1) {
+static const void* g3_kernel(int mt, int wn, int planes) {
+    if (planes == 1) {
         if (wn == 2)
             return mt == 8 ? (const void*)k_gemm_bf16<MODE, 3, 8, 2>
                  : mt == 4 ? (const void*)k_gemm_bf16<MODE, 3, 4, 2> : mt == 3 ? (const void*)k_gemm_bf16<MODE, 3, 3, 2>
@@ -744,18 +740,18 @@ static bool g3_some_tile_ok(int Tc, bool conv = false) {
 struct G3Launch { Gemm3Args ax; int grid, lds, threads; const void* kern; };
 
 // everything of a k_gemm_bf16x3 launch but the launch itself: kernel instance, LDS size, block order, grid
-static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, G3Launch* L) {
+static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, int planes, G3Launch* L) {
     // LIF_REG owns its CU (256 registers per wave); the others run two work-groups per CU
     const void* kern;
     int lds = G3_LDS(wn == 1 ? G3_NB1 : 3, wn), tiles = cdiv(a.M, g3_bm(wn, mt));
     const int threads = mt == 8 ? 256 : 512;
     const int tile_lds = (wn == 2 ? G3_TILE_BYTES(2) : G3_TILE_BYTES(1)) + G3_CNT_BYTES;   // the LIF_TILE epilogue reuses the ring (+ per-position spike counts)
     switch (mode) {
-    case G3_FC: kern = g3_kernel<G3_FC>(mt, wn); break;
-    case G3_CONV: kern = g3_kernel<G3_CONV>(mt, wn); break;
-    case G3_CONV_LIF_REG: kern = g_weight_planes == 1 ? (const void*)k_gemm_bf16<G3_CONV_LIF_REG, 3, 4, 2> : (const void*)k_gemm_bf16x3<G3_CONV_LIF_REG, 3, 4, 2>; lds = G3_LDS(3, 2) + G3_STATE_BYTES; break;
-    case G3_CONV_LIF_TILE: kern = g3_kernel<G3_CONV_LIF_TILE>(mt, wn); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
-    default: kern = g3_kernel<G3_FC_LIF_TILE>(mt, wn); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
+    case G3_FC: kern = g3_kernel<G3_FC>(mt, wn, planes); break;
+    case G3_CONV: kern = g3_kernel<G3_CONV>(mt, wn, planes); break;
+    case G3_CONV_LIF_REG: kern = planes == 1 ? (const void*)k_gemm_bf16<G3_CONV_LIF_REG, 3, 4, 2> : (const void*)k_gemm_bf16x3<G3_CONV_LIF_REG, 3, 4, 2>; lds = G3_LDS(3, 2) + G3_STATE_BYTES; break;
+    case G3_CONV_LIF_TILE: kern = g3_kernel<G3_CONV_LIF_TILE>(mt, wn, planes); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
+    default: kern = g3_kernel<G3_FC_LIF_TILE>(mt, wn, planes); tiles = cdiv(a.M, a.pb); lds = max(lds, tile_lds); break;
     }
     static_assert(2 * (G3_TILE_BYTES(1) + G3_CNT_BYTES) <= 160 * 1024 && 2 * G3_LDS(3, 2) <= 160 * 1024, "two work-groups per CU");
     // XCD-aware order for launches with 4, 8 or 16 column blocks whose weight panels are small enough to stay in an XCD's L2
@@ -765,7 +761,7 @@ static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, G3Launch*
     ax.n_tiles = tiles; ax.xcd_classes = 0;
     ax.epi_general = knobs().epi_general;
     int grid = tiles * a.n_blocks;
-    const size_t pair_bytes = (size_t)2 * G3_BN(wn) * a.Kc * 32 * 2 * g_weight_planes;
+    const size_t pair_bytes = (size_t)2 * G3_BN(wn) * a.Kc * 32 * 2 * planes;
     const bool conv_mode = mode == G3_CONV || mode == G3_CONV_LIF_TILE;
     if (knobs().bf16x3_xcd && mt != 8 && conv_mode && (a.n_blocks == 2 || (a.n_blocks == 4 && pair_bytes <= (size_t)2 << 20)) && tiles >= 64) {
         // 3x3 convolution with two / four column blocks: half of them and a contiguous quarter of the row tiles per XCD (halo rows stay
@@ -784,9 +780,9 @@ static int prepare_gemm3(int mode, int mt, int wn, const Gemm3Args& a, G3Launch*
     return 0;
 }
 
-static int launch_gemm3(int mode, int mt, int wn, const Gemm3Args& a, hipStream_t s) {
+static int launch_gemm3(int mode, int mt, int wn, const Gemm3Args& a, int planes, hipStream_t s) {
     G3Launch L;
-    prepare_gemm3(mode, mt, wn, a, &L);
+    prepare_gemm3(mode, mt, wn, a, planes, &L);
     hipError_t e = hipFuncSetAttribute(L.kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     if (knobs().debug_occ) {                                   // debug: co-resident work-groups per CU
@@ -801,9 +797,6 @@ static int launch_gemm3(int mode, int mt, int wn, const Gemm3Args& a, hipStream_
     SNN_CHECK_LAUNCH("k_gemm_bf16x3");
     return 0;
 }
-
-// (declared further down)
-static bool g3_tile_ok(int T, int rows);
 
 int snn_debug_encoder_thresholds(const snn_params* p, float* th32) {
     static_assert(SNN_MAX_STEPS == 32, "EncTh holds 32 thresholds");
@@ -839,8 +832,8 @@ int snn_debug_last_fc6_path(void) { return g_last_fc_sparse; }
 void snn_debug_last_rpn_planes(unsigned long long* out3) { if (out3) for (int i = 0; i < 3; ++i) out3[i] = g_last_rpn_planes[i]; }
 void snn_debug_last_det_planes(unsigned long long* out3) { if (out3) for (int i = 0; i < 3; ++i) out3[i] = g_last_det_planes[i]; }
 
-int snn_spike_gemm_bf16x3(const uint32_t* a_rows, int M, int K, int N, const uint16_t* w_packed, float* cur, int ldo,
-                          snn_stream_t s) {
+static int spike_gemm_bf16x3_impl(const uint32_t* a_rows, int M, int K, int N, const uint16_t* w_packed, float* cur, int ldo, int planes,
+                                  snn_stream_t s) {
     if (!a_rows || !w_packed || !cur || M <= 0 || K <= 0 || N <= 0 || ldo < N)
         return fail(-1, "snn_spike_gemm_bf16x3: bad argument");
     Gemm3Args a;
@@ -851,7 +844,12 @@ int snn_spike_gemm_bf16x3(const uint32_t* a_rows, int M, int K, int N, const uin
     const int wn = g3_wn();
     a.n_blocks = cdiv(a.Np, G3_BN(wn));
     const int mt = g3_pick_mt([&](int m) { return (long long)cdiv(M, g3_bm(wn, m)) * a.n_blocks; });
-    return launch_gemm3(G3_FC, mt, wn, a, (hipStream_t)s);
+    return launch_gemm3(G3_FC, mt, wn, a, planes, (hipStream_t)s);
+}
+
+int snn_spike_gemm_bf16x3(const uint32_t* a_rows, int M, int K, int N, const uint16_t* w_packed, float* cur, int ldo,
+                          snn_stream_t s) {
+    return spike_gemm_bf16x3_impl(a_rows, M, K, N, w_packed, cur, ldo, 3, s);
 }
 
 // period planes: row group n - 1 of a tile holds u_n = W e_n; the current of step t < Tc is the sum over the divisors n <= Tc of t + 1
@@ -901,7 +899,7 @@ static int spike_gemm_lif_bf16x3_impl(const uint32_t* a_planes, int T, int R, in
     G3Tile tl;
     const int rc = spike_gemm_lif_bf16x3_args(a_planes, T, R, K, N, p, w_packed, spk, spk_stride, row_counts, wm_in, wm_out, win, periods, &a, &tl);
     if (rc) return rc;
-    return launch_gemm3(G3_FC_LIF_TILE, tl.mt, g3_wn(), a, (hipStream_t)s);
+    return launch_gemm3(G3_FC_LIF_TILE, tl.mt, g3_wn(), a, 3, (hipStream_t)s);
 }
 
 int snn_spike_gemm_lif_bf16x3(const uint32_t* a_planes, int T, int R, int K, int N, const snn_params* p,
@@ -1195,8 +1193,8 @@ static bool sparse_plan(int Tc, SparsePlan* sp, long long units = 0, int n_block
 // linear: any T whose window (T - 2, or T - 1 in spike-rate mode) fits the slot grid - 4 .. 24 planes on the 4 x 2 wave grid - with the
 // general LIF epilogue outside the straight-line grid (round 5: T_det = 17 .. 26 and spike-rate mode used to take the all-dense launch).
 struct SparseShape { SparsePlan sp; int n_tiles, n_blocks, grid, lds, xcd_cpx, xcd_contig, epi_general; };
-static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, int Tc, SparseShape* out) {
-    if (!knobs().sparse || (conv ? g_conv_route.route : g_fc6_route.route) == SNN_ROUTE_DENSE || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
+static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, int Tc, const SparseRoute& rt, SparseShape* out) {
+    if (!knobs().sparse || rt.route == SNN_ROUTE_DENSE || Kw % 2 || Np % 64 || Kc * 32 > 65536 || M <= 0) return false;
     if (conv ? (T < 5 || T > 16 || Tc != T - 1) : (T < 5 || T > SNN_MAX_STEPS || (Tc != T - 2 && Tc != T - 1))) return false;
     if (!sparse_plan(Tc, &out->sp, conv ? 0 : M, Np / 64)) return false;
     const SparsePlan& sp = out->sp;
@@ -1220,17 +1218,17 @@ static bool sparse_shape(bool conv, long long M, int Kw, int Kc, int Np, int T, 
 // the sparse launch pair: compress the planes e_3 .., then the mixed dense / sparse contraction + LIF (conv: the RPN's shared 3x3
 // convolution; !conv: a linear layer on word-major period planes - the detector's fc6).  `side` = sparse_side_bytes() of scratch.
 // Returns 1 if the launches were enqueued (the layer is done), 0 if this configuration takes the dense launch, negative on error;
-// 2 on the gated conv / fc6 route (g_conv_route.gated, g_fc6_route.gated: compress + count, the decision, and this launch behind the gate -
-// the caller enqueues the dense launch behind the same gate).
+// 2 on the gated conv / fc6 route (rt.gated: compress + count, the decision, and this launch behind the gate - the caller enqueues the dense
+// launch behind the same gate).  planes: weight planes of the launch (weight_planes).
 // (Every eligibility check comes before the first launch: a configuration that ends on the dense kernel enqueues nothing here.)
 // mode: SPARSE_RUN = compress + launch; SPARSE_QUERY = would it run? (nothing is enqueued); SPARSE_RUN_COMPRESSED = the caller's encoder has
 // already written the compressed planes into `side` (RPN head: encode_block, snn_encode.h)
 enum { SPARSE_RUN = 0, SPARSE_QUERY = 1, SPARSE_RUN_COMPRESSED = 2 };
-static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t side_bytes, hipStream_t s, int mode = SPARSE_RUN) {
+static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t side_bytes, hipStream_t s, int mode, const SparseRoute& rt, int planes) {
     SparseShape sh;
     const int Kw = conv ? a.Cw : a.Kc;                        // plane words per row
     if (!side || !a.wm || !a.periods || a.t0 != 0 || a.p.v_leak != 0.0f || (float)(a.p.v_leak - a.p.v_th) > 0.0f || (!conv && !a.out_wm) ||
-        !sparse_shape(conv, a.M, Kw, a.Kc, a.Np, a.T, a.Tc, &sh))      // (the plan does not depend on spike counting; whether the LIF runs in registers does: sparse_plan_lif_regs below)
+        !sparse_shape(conv, a.M, Kw, a.Kc, a.Np, a.T, a.Tc, rt, &sh))      // (the plan does not depend on spike counting; whether the LIF runs in registers does: sparse_plan_lif_regs below)
         return 0;
     const SparsePlan& sp = sh.sp;
     const long long P = a.M, Pe = (long long)a.a_step;
@@ -1242,12 +1240,11 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     if (mode == SPARSE_QUERY) return 1;
     const void* kern = sp.fat ? (conv ? (sp.wn == 1 ? (const void*)k_gemm_lif_sparse<true, 1, true> : (const void*)k_gemm_lif_sparse<true, 2, true>) : (const void*)k_gemm_lif_sparse<false, 2, true>)
                               : conv ? (const void*)k_gemm_lif_sparse<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse<false, 2> : (const void*)k_gemm_lif_sparse<false, 1>;
-    if (g_weight_planes == 1)
+    if (planes == 1)
         kern = sp.fat ? (conv ? (sp.wn == 1 ? (const void*)k_gemm_lif_sparse1<true, 1, true> : (const void*)k_gemm_lif_sparse1<true, 2, true>) : (const void*)k_gemm_lif_sparse1<false, 2, true>)
                       : conv ? (const void*)k_gemm_lif_sparse1<true, 1> : sp.wn == 2 ? (const void*)k_gemm_lif_sparse1<false, 2> : (const void*)k_gemm_lif_sparse1<false, 1>;
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, sh.lds);
     if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    const ConvRoute& rt = conv ? g_conv_route : g_fc6_route;
     const bool gated = rt.gated;
     if (gated && (mode != SPARSE_RUN || !rt.stat || a.cnt_img || a.cnt_row)) return fail(-3, "conv / fc6 route: gated launch outside its plan (internal)");
     if (mode != SPARSE_RUN_COMPRESSED) {
@@ -1307,7 +1304,7 @@ static int gemm3_lif_sparse(const Gemm3Args& a, bool conv, void* side, size_t si
     // round 6: the FAT conv on 4 x 1 waves (T = 7 .. 9, LIF in registers) in its ping-pong form - one persistent work-group of 8 waves per CU
     // (snn_sparse_pp.h); same plan, same arguments, bit-identical planes
     const int pp_ns = a.Tc - sp.nd;
-    if (g_weight_planes == 3 && conv && !gated && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
+    if (planes == 3 && conv && !gated && sp.fat && sp.wn == 1 && sa.lif_regs && knobs().conv_pp && sp.nd == 2 && pp_ns >= 4 && pp_ns <= 5 && sa.Kc >= 4) {      // (T = 7, 8; at T = 9 the 8-wave work-group has no register left: 68 bytes of scratch)
         const void* kpp = pp_ns == 4 ? (const void*)k_conv_lif_pp<4> : (const void*)k_conv_lif_pp<5>;
         e = hipFuncSetAttribute(kpp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
@@ -1348,7 +1345,7 @@ int snn_debug_tile_shape(int conv, long long units, int k_in, int n_cols, int nu
     // the structured-sparse plan, where the launchers take it (period planes of the default parameters: conv, fc6)
     SparseShape sh;
     const int Kw = cdiv(k_in, 32), Np = cdiv(n_cols, 32) * 32;
-    if (knobs().periods && (conv || layer != 7) && sparse_shape(conv != 0, units, Kw, conv ? 9 * Kw : Kw, Np, num_steps, Tc, &sh)) {      // (spike_rates only moves a linear layer's window: Tc above)
+    if (knobs().periods && (conv || layer != 7) && sparse_shape(conv != 0, units, Kw, conv ? 9 * Kw : Kw, Np, num_steps, Tc, SPARSE_ROUTE, &sh)) {      // (spike_rates only moves a linear layer's window: Tc above)
         const SparsePlan& sp = sh.sp;
         int slots = 0;
         for (int w = 0; w < (sp.fat ? 4 : 8) / sp.wn; ++w) slots += sp.w_nd[w] + sp.w_ns[w];
@@ -1365,16 +1362,26 @@ int snn_debug_tile_shape(int conv, long long units, int k_in, int n_cols, int nu
     return 0;
 }
 
+// what the conv + LIF launcher is told beyond the layer itself (the defaults: a stage-level call on row-major planes)
+struct ConvLifOpts {
+    bool wm = false;                     // encoder planes word-major [T][Cw][rows]
+    bool* out_split = nullptr;           // (in: wanted, out: done) spike planes in blocks of four words (Gemm3Args.out_split; T-in-tile kernels only)
+    bool periods = false;                // the encoder wrote period planes
+    void* sparse_side = nullptr;         // side buffers of the structured-sparse launch (sparse_side_bytes)
+    size_t sparse_bytes = 0;
+    // SPARSE_QUERY: returns 1 if this call would enqueue the structured-sparse launch pair, 0 if not - and enqueues nothing;
+    // SPARSE_RUN_COMPRESSED: the encoder wrote the planes e_3 .. compressed (and not raw): anything but the sparse launch is an error
+    int sparse_mode = SPARSE_RUN;
+    SparseRoute route = SPARSE_ROUTE;
+    int planes = 3;                      // weight planes (weight_planes)
+};
 static int conv3x3_lif_bf16x3_impl(const uint32_t* enc, size_t enc_stride, const snn_rpn_level* lv, int n_levels, int C_in,
                                    int C_out, int T, const snn_params* p, const uint16_t* w_packed, uint32_t* spk,
-                                   size_t spk_stride, unsigned long long* counts, int max_n, snn_stream_t s, bool wm = false,
-                                   bool* out_split = nullptr, bool periods = false, void* sparse_side = nullptr, size_t sparse_bytes = 0,
-                                   int sparse_mode = SPARSE_RUN) {
-    // sparse_mode SPARSE_QUERY: returns 1 if this call would enqueue the structured-sparse launch pair, 0 if not - and enqueues nothing;
-    // SPARSE_RUN_COMPRESSED: the encoder wrote the planes e_3 .. compressed (and not raw): anything but the sparse launch is an error
-    // out_split (in: wanted, out: done): spike planes in blocks of four words (Gemm3Args.out_split; T-in-tile kernels only)
-    const bool want_split = out_split && *out_split;
-    if (out_split) *out_split = false;
+                                   size_t spk_stride, unsigned long long* counts, int max_n, snn_stream_t s, const ConvLifOpts& o) {
+    const bool wm = o.wm, periods = o.periods;
+    const int sparse_mode = o.sparse_mode;
+    const bool want_split = o.out_split && *o.out_split;
+    if (o.out_split) *o.out_split = false;
     if (!spk || !p) return fail(-1, "snn_conv3x3_lif_bf16x3: bad argument");
     Gemm3Args a;
     long long P;
@@ -1400,30 +1407,31 @@ static int conv3x3_lif_bf16x3_impl(const uint32_t* enc, size_t enc_stride, const
         if (sparse_mode == SPARSE_QUERY) return 0;
         if (periods) return fail(-4, "snn_conv3x3_lif_bf16x3: period planes need the T-in-tile kernel (T=%d does not fit a row tile)", T);
         a.n_blocks = cdiv(a.Np, G3_BN(2));
-        rc = launch_gemm3(G3_CONV_LIF_REG, 4, 2, a, (hipStream_t)s);
+        rc = launch_gemm3(G3_CONV_LIF_REG, 4, 2, a, o.planes, (hipStream_t)s);
         if (rc || !counts) return rc;
         return count_spikes_per_image(lv, n_levels, cdiv(C_out, 32), T, spk, spk_stride, counts, max_n, (hipStream_t)s);
     }
     a.pb = tl.rows / Tc; a.n_short = tl.n_short;
     a.cnt_img = counts; a.max_n = max_n;
-    if (want_split && a.Np % 128 == 0) { a.out_split = 1; *out_split = true; }
+    if (want_split && a.Np % 128 == 0) { a.out_split = 1; *o.out_split = true; }
     if (periods && set_periods(a, "snn_conv3x3_lif_bf16x3")) return -1;
     // round 4: the sparse period planes on the structured-sparse matrix-core instruction (snn_sparse.h) where the configuration allows
-    rc = gemm3_lif_sparse(a, true, sparse_side, sparse_bytes, (hipStream_t)s, sparse_mode);
+    rc = gemm3_lif_sparse(a, true, o.sparse_side, o.sparse_bytes, (hipStream_t)s, sparse_mode, o.route, o.planes);
     if (sparse_mode == SPARSE_QUERY) return rc > 0 ? 1 : 0;
     if (rc < 0) return rc;
     g_last_conv_sparse = rc;
     if (rc == 1) return 0;
-    if (rc == 2) { a.gate = (const int*)g_conv_route.stat + 2; a.gate_want = 1; }      // the gated route: the dense launch on the raw period planes, behind the same word
+    if (rc == 2) { a.gate = (const int*)o.route.stat + 2; a.gate_want = 1; }      // the gated route: the dense launch on the raw period planes, behind the same word
     if (sparse_mode == SPARSE_RUN_COMPRESSED) return fail(-3, "snn_conv3x3_lif_bf16x3: the encoder wrote compressed planes but the conv takes the dense launch (internal)");
-    return launch_gemm3(G3_CONV_LIF_TILE, tl.mt, wn, a, (hipStream_t)s);
+    return launch_gemm3(G3_CONV_LIF_TILE, tl.mt, wn, a, o.planes, (hipStream_t)s);
 }
 
 int snn_conv3x3_lif_bf16x3(const uint32_t* enc, size_t enc_stride, const snn_rpn_level* lv, int n_levels, int C_in,
                            int C_out, int T, const snn_params* p, const uint16_t* w_packed, uint32_t* spk,
                            size_t spk_stride, snn_stream_t s) {
-    return conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C_in, C_out, T, p, w_packed, spk, spk_stride, nullptr, 0, s,
-                                   knobs().stage_wm, nullptr, knobs().stage_periods && !knobs().bf16x3_lif_reg);
+    ConvLifOpts o;
+    o.wm = knobs().stage_wm; o.periods = knobs().stage_periods && !knobs().bf16x3_lif_reg;
+    return conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C_in, C_out, T, p, w_packed, spk, spk_stride, nullptr, 0, s, o);
 }
 
 // spikes per (level, image) from finished planes: one launch per level (fallback of the register-fused conv variant only)
@@ -1451,7 +1459,7 @@ int snn_spike_conv3x3_bf16x3(const uint32_t* enc, size_t enc_stride, const snn_r
     const int wn = g3_wn(true);
     a.n_blocks = cdiv(a.Np, G3_BN(wn));
     const int mt = g3_pick_mt([&](int m) { return (long long)cdiv(a.M, g3_bm(wn, m)) * a.n_blocks; });
-    return launch_gemm3(G3_CONV, mt, wn, a, (hipStream_t)s);
+    return launch_gemm3(G3_CONV, mt, wn, a, 3, (hipStream_t)s);
 }
 
 static int check_T(int T, const char* who) {
@@ -2010,30 +2018,50 @@ size_t snn_rpn_head_workspace_bytes(const snn_rpn_level* lv, int n_levels, int C
     return tot;
 }
 
-// an RPN pass with any-time readouts (snn_rpn_head_forward_readouts): outputs [n][P][A] / [n][P][4A], counts [n][n_levels][max_n]
-struct RpnReadouts { const int* steps; int n; };
+// everything an RPN head pass is told, whichever exported entry it came through (the entries check what is theirs alone - the step list, the
+// pairs that go together, the route - fill one of these and run it)
+struct RpnCall {
+    const snn_rpn_level* lv; int fdt, n_levels, C, A, T;      // the feed: typed feature maps per level; T: the pass's last step
+    const snn_params* p;
+    const void* w_shared_packed; const float* w_heads_packed;
+    float *out_logits, *out_bbox; unsigned long long* spike_counts; float *sum_logits, *sum_bbox;
+    void* ws; size_t ws_bytes; snn_stream_t stream;
+    int stage_mask;
+    // any-time readouts (snn_rpn_head_forward_readouts): outputs [n][P][A] / [n][P][4A], counts [n][n_levels][max_n]; null: one readout at T
+    const int* steps; int n_steps;
+    SparseRoute route;                                         // of the conv; .gated is the plan's to decide, not the entry's
+    const char* who;                                           // the name in messages
+};
+static RpnCall rpn_call(const snn_rpn_level* lv, int fdt, int n_levels, int C, int A, int T, const snn_params* p, const void* w_shared_packed,
+                        const float* w_heads_packed, float* out_logits, float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
+                        float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    return RpnCall{lv, fdt, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits, sum_bbox,
+                   ws, ws_bytes, stream, SNN_STAGE_ALL, nullptr, 0, SPARSE_ROUTE, "snn_rpn_head_forward"};
+}
 
 // the RPN head: encoder, conv + LIF, then the LI heads - one readout at T (the plain forward), or the readout set with its spike counts
-static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
-                         const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
-                         float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
-                         float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, const RpnReadouts* ro, snn_stream_t stream,
-                         int fdt = SNN_FEAT_F32) {
-    if (!lv || !p || !w_shared_packed || !w_heads_packed || !out_logits || !out_bbox || !ws)
-        return fail(-1, "snn_rpn_head_forward: null argument");
-    if (n_levels <= 0 || n_levels > SNN_MAX_LEVELS) return fail(-1, "snn_rpn_head_forward: n_levels=%d", n_levels);
-    if (C <= 0 || A <= 0) return fail(-1, "snn_rpn_head_forward: bad C/A");
+static int rpn_head_run(const RpnCall& c) {
+    const snn_rpn_level* const lv = c.lv;
+    const int fdt = c.fdt, n_levels = c.n_levels, C = c.C, A = c.A, T = c.T, stage_mask = c.stage_mask;
+    const snn_params* const p = c.p;
+    const void* const w_shared_packed = c.w_shared_packed;
+    unsigned long long* const spike_counts = c.spike_counts;
+    void* const ws = c.ws;
+    const snn_stream_t stream = c.stream;
+    if (!lv || !p || !w_shared_packed || !c.w_heads_packed || !c.out_logits || !c.out_bbox || !ws)
+        return fail(-1, "%s: null argument", c.who);
+    if (n_levels <= 0 || n_levels > SNN_MAX_LEVELS) return fail(-1, "%s: n_levels=%d", c.who, n_levels);
+    if (C <= 0 || A <= 0) return fail(-1, "%s: bad C/A", c.who);
     if (prec_family(p) != SNN_PRECISION_F32 && prec_family(p) != SNN_PRECISION_BF16X3 && prec_family(p) != SNN_PRECISION_MXFP6)
-        return fail(-1, "snn_rpn_head_forward: unknown precision %d", p->precision);
+        return fail(-1, "%s: unknown precision %d", c.who, p->precision);
     if (prec_family(p) == SNN_PRECISION_MXFP6 && (C % 128 || !mx_tile_ok(lif_window_full_out(T).n)))
-        return fail(-4, "snn_rpn_head_forward: the mxfp6 kernels need C %% 128 == 0 and a T that fits a 512-row tile (C=%d, T=%d)", C, T);
-    if (check_T(T, "snn_rpn_head_forward")) return -1;
-    const WeightPlanesScope planes(p);
+        return fail(-4, "%s: the mxfp6 kernels need C %% 128 == 0 and a T that fits a 512-row tile (C=%d, T=%d)", c.who, C, T);
+    if (check_T(T, c.who)) return -1;
     for (int l = 0; l < n_levels; ++l)
         if (!lv[l].feat || lv[l].N <= 0 || lv[l].H <= 0 || lv[l].W <= 0)
-            return fail(-1, "snn_rpn_head_forward: bad level %d", l);
+            return fail(-1, "%s: bad level %d", c.who, l);
     for (int l = 0; l < n_levels; ++l)
-        if (check_feat(lv[l].feat, fdt, "snn_rpn_head_forward")) return -1;
+        if (check_feat(lv[l].feat, fdt, c.who)) return -1;
     const bool nhwc = (fdt & SNN_FEAT_NHWC) != 0;
     if (nhwc && C % 32) return SNN_STATUS_NO_TYPED_KERNEL;       // (channels-last kernels: whole channel words only; nothing enqueued)
     int max_n = 0;
@@ -2042,7 +2070,7 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
     const bool mxp = prec_family(p) != SNN_PRECISION_F32;            // encoder planes with a zero halo (k_gemm_bf16x3, k_gemm_mx)
     const long long Pe = mxp ? rpn_positions_padded(lv, n_levels) : P;
     rpn_ws_layout(P, mxp ? Pe : 0, C, T, prec_family(p), &o_spk, &o_cur, &o_cnt, &need);
-    if (ws_bytes < need) return fail(-2, "snn_rpn_head_forward: workspace %zu < %zu bytes", ws_bytes, need);
+    if (c.ws_bytes < need) return fail(-2, "%s: workspace %zu < %zu bytes", c.who, c.ws_bytes, need);
     const int Cw = cdiv(C, 32);
     const size_t stride = (size_t)P * Cw;            // words per time plane (spike planes)
     const size_t enc_stride = (size_t)Pe * Cw;       // ... of the encoder planes
@@ -2070,23 +2098,28 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
     // the two stages cannot disagree - also for a stage-by-stage caller
     // conv route AUTO (snn_rpn_head_forward_routed): where the plan is the sparse one - and the call counts no spikes - the encoder leaves every
     // period plane raw (the form the dense launch reads), and the conv stage enqueues compress + count, the decision and both launches behind the
-    // gate word; every other configuration runs its plan as it is
-    bool fold = false, route_gated = false;
+    // gate word (co.route.gated); every other configuration runs its plan as it is
+    ConvLifOpts co;
+    co.wm = wm_rows != 0; co.out_split = &split; co.periods = per; co.sparse_side = (char*)ws + o_cur; co.sparse_bytes = o_cnt - o_cur;
+    co.route = c.route; co.planes = weight_planes(p);
+    bool fold = false;
     {
         NeuronP npq = make_p(p, p->v_th_enc);
         if (per) npq.v_fire = ENC_FIRED;
         const EncTh* ethq;
-        const bool want_auto = g_conv_route.route == SNN_ROUTE_AUTO && !spike_counts && stage_mask == SNN_STAGE_ALL;
+        const bool want_auto = c.route.route == SNN_ROUTE_AUTO && !spike_counts && stage_mask == SNN_STAGE_ALL;
         const bool may_fold = knobs().enc_fold && enc_mode(npq, &ethq) == ENC_QUANT;
         if (prec_family(p) == SNN_PRECISION_BF16X3 && per && wm_rows && (may_fold || want_auto)) {
             bool split_q = split;
+            ConvLifOpts q = co;
+            q.out_split = &split_q; q.sparse_mode = SPARSE_QUERY;
             const bool sparse_plan = conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint16_t*)w_shared_packed, spk, stride, spike_counts,
-                                                             max_n, stream, true, &split_q, per, (char*)ws + o_cur, o_cnt - o_cur, SPARSE_QUERY) == 1;
-            route_gated = sparse_plan && want_auto;
-            fold = sparse_plan && may_fold && !route_gated;
+                                                             max_n, stream, q) == 1;
+            co.route.gated = sparse_plan && want_auto;
+            fold = sparse_plan && may_fold && !co.route.gated;
         }
     }
-    g_conv_route.gated = route_gated;
+    co.sparse_mode = fold ? SPARSE_RUN_COMPRESSED : SPARSE_RUN;
     uint32_t* enc_cmp = fold ? (uint32_t*)((char*)ws + o_cur) : nullptr;
     if (stage_mask & SNN_STAGE_ENCODE) {                        // rpn.py:101, all levels in one launch
         EncLevels el;
@@ -2094,7 +2127,7 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
         long long pos = 0;
         int blocks = 0;
         for (int l = 0; l < n_levels; ++l) {
-            if (!lv[l].feat) return fail(-1, "snn_rpn_head_forward: level %d has no features", l);
+            if (!lv[l].feat) return fail(-1, "%s: level %d has no features", c.who, l);
             el.feat[l] = lv[l].feat; el.HW[l] = lv[l].H * lv[l].W; el.bpi[l] = cdiv(el.HW[l], ENC_PB);
             el.blk_base[l] = blocks; el.pos_base[l] = (int)pos; el.Wpad[l] = mxp ? lv[l].W : 0;
             blocks += lv[l].N * el.bpi[l];
@@ -2133,31 +2166,29 @@ static int rpn_head_impl(const snn_rpn_level* lv, int n_levels, int C, int A, in
                          ? conv3x3_lif_mx_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint32_t*)w_shared_packed, spk, stride,
                                                spike_counts, max_n, stream)
                          : conv3x3_lif_bf16x3_impl(enc, enc_stride, lv, n_levels, C, C, T, p, (const uint16_t*)w_shared_packed,
-                                                   spk, stride, spike_counts, max_n, stream, wm_rows != 0, &split, per,
-                                                   (char*)ws + o_cur, o_cnt - o_cur, fold ? SPARSE_RUN_COMPRESSED : SPARSE_RUN);
-            g_conv_route.gated = false;
+                                                   spk, stride, spike_counts, max_n, stream, co);
             if (rc) return rc;
             conv_sparse = prec_family(p) == SNN_PRECISION_BF16X3 ? g_last_conv_sparse : 0;
         }
         // route_stat of a call that did not decide on the device: {0, 0, 0 = the sparse launch ran (and always in spike-rate mode) / 1 = dense, 0}
-        if (g_conv_route.stat && conv_sparse != 2) {
-            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_conv_route.stat, (const int*)nullptr, 0, 0, 0.0f, (spike_counts || conv_sparse) ? 0 : 1);
+        if (c.route.stat && conv_sparse != 2) {
+            hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)c.route.stat, (const int*)nullptr, 0, 0, 0.0f, (spike_counts || conv_sparse) ? 0 : 1);
             SNN_CHECK_LAUNCH("k_route_decide");
         }
     }
     g_last_rpn_planes[0] = o_spk; g_last_rpn_planes[1] = split ? 1 : 0; g_last_rpn_planes[2] = (unsigned long long)P;
     if (!(stage_mask & SNN_STAGE_LI_HEADS)) return 0;
-    if (!ro)
-        return li_heads_impl(spk, stride, T, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox, sum_logits,
-                             sum_bbox, split, stream);
-    int rc = li_heads_readouts_impl(spk, stride, ro->steps, ro->n, (int)P, C, w_heads_packed, A, 4 * A, p, out_logits, out_bbox,
-                                    sum_logits, sum_bbox, split, stream);
+    if (!c.steps)
+        return li_heads_impl(spk, stride, T, (int)P, C, c.w_heads_packed, A, 4 * A, p, c.out_logits, c.out_bbox, c.sum_logits,
+                             c.sum_bbox, split, stream);
+    int rc = li_heads_readouts_impl(spk, stride, c.steps, c.n_steps, (int)P, C, c.w_heads_packed, A, 4 * A, p, c.out_logits, c.out_bbox,
+                                    c.sum_logits, c.sum_bbox, split, stream);
     if (rc || !spike_counts) return rc;
     // [n][n_levels][max_n]: popcounts of the shared LIF's planes t < T'_j per (level, image).  The conv above ran as a spike-rate
     // forward at T (same launch) and left its counts in the first rows of spike_counts: zeroed and overwritten here
-    if (hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * ro->n * n_levels * max_n, s) != hipSuccess)
+    if (hipMemsetAsync(spike_counts, 0, sizeof(unsigned long long) * c.n_steps * n_levels * max_n, s) != hipSuccess)
         return fail(-3, "hipMemsetAsync failed");
-    const StepList st = step_list(ro->steps, ro->n);
+    const StepList st = step_list(c.steps, c.n_steps);
     long long pb = 0;
     for (int l = 0; l < n_levels; ++l) {
         const int hw = lv[l].H * lv[l].W;
@@ -2183,8 +2214,10 @@ int snn_rpn_head_forward_stages_typed(const snn_rpn_level* lv, int fdt, int n_le
                                       const void* w_shared_packed, const float* w_heads_packed, float* out_logits,
                                       float* out_bbox, unsigned long long* spike_counts, float* sum_logits,
                                       float* sum_bbox, void* ws, size_t ws_bytes, int stage_mask, snn_stream_t stream) {
-    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
-                         sum_bbox, ws, ws_bytes, stage_mask, nullptr, stream, fdt);
+    RpnCall c = rpn_call(lv, fdt, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits, sum_bbox,
+                         ws, ws_bytes, stream);
+    c.stage_mask = stage_mask;
+    return rpn_head_run(c);
 }
 
 int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p,
@@ -2198,7 +2231,7 @@ int snn_rpn_head_forward(const snn_rpn_level* lv, int n_levels, int C, int A, in
 // the routed forward's workspace: the plain forward's.  Its first plane set holds the raw planes of every period (the encoder form of the dense
 // plan), its side buffer the compressed planes; the gate word is route_stat[2], in the caller's array
 size_t snn_rpn_head_workspace_bytes_routed(const snn_rpn_level* lv, int n_levels, int C, int A, int T, int precision, int route) {
-    if (route != SNN_ROUTE_SPARSE && route != SNN_ROUTE_DENSE && route != SNN_ROUTE_AUTO) return 0;
+    if (!route_known(route)) return 0;
     return snn_rpn_head_workspace_bytes(lv, n_levels, C, A, T, precision);
 }
 
@@ -2206,17 +2239,13 @@ int snn_rpn_head_forward_routed(const snn_rpn_level* lv, int fdt, int n_levels, 
                                 const void* w_shared_packed, const float* w_heads_packed, float* out_logits, float* out_bbox,
                                 unsigned long long* spike_counts, float* sum_logits, float* sum_bbox, void* ws, size_t ws_bytes,
                                 int route, float crossover, int32_t* route_stat, snn_stream_t stream) {
-    if (route != SNN_ROUTE_SPARSE && route != SNN_ROUTE_DENSE && route != SNN_ROUTE_AUTO)
-        return fail(-1, "snn_rpn_head_forward_routed: unknown route %d", route);
-    if (route == SNN_ROUTE_AUTO && !route_stat) return fail(-1, "snn_rpn_head_forward_routed: SNN_ROUTE_AUTO needs route_stat");
-    if (route == SNN_ROUTE_AUTO && crossover != crossover) return fail(-1, "snn_rpn_head_forward_routed: crossover is not a number");
-    if (lv && p && n_levels > 0 && n_levels <= SNN_MAX_LEVELS && C > 0 && T >= 1) {      // (anything else: rpn_head_impl's own message)
-        const size_t need = snn_rpn_head_workspace_bytes_routed(lv, n_levels, C, A, T, p->precision, route);
-        if (ws_bytes < need) return fail(-1, "snn_rpn_head_forward_routed: workspace %zu < %zu bytes", ws_bytes, need);
-    }
-    const ConvRouteScope scope(spike_counts ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);      // (spike-rate mode: today's plan on every route)
-    return rpn_head_impl(lv, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
-                         sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, nullptr, stream, fdt);
+    // (no p, or a shape the size query answers with 0: the pass's own message)
+    const size_t need = p ? snn_rpn_head_workspace_bytes_routed(lv, n_levels, C, A, T, p->precision, route) : 0;
+    if (route_check("snn_rpn_head_forward_routed", route, crossover, route_stat, ws_bytes, need)) return -1;
+    RpnCall c = rpn_call(lv, fdt, n_levels, C, A, T, p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits, sum_bbox,
+                         ws, ws_bytes, stream);
+    c.route = routed(route, crossover, route_stat, spike_counts != nullptr);
+    return rpn_head_run(c);
 }
 
 int snn_rpn_head_forward_readouts(const snn_rpn_level* lv, int n_levels, int C, int A, const int* steps, int n_steps,
@@ -2233,9 +2262,10 @@ int snn_rpn_head_forward_readouts_typed(const snn_rpn_level* lv, int fdt, int n_
                                         void* ws, size_t ws_bytes, snn_stream_t stream) {
     if (check_steps(steps, n_steps, "snn_rpn_head_forward_readouts")) return -1;
     if ((sum_logits == nullptr) != (sum_bbox == nullptr)) return fail(-1, "snn_rpn_head_forward_readouts: sum_logits and sum_bbox go together");
-    const RpnReadouts ro{steps, n_steps};
-    return rpn_head_impl(lv, n_levels, C, A, steps[n_steps - 1], p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts,
-                         sum_logits, sum_bbox, ws, ws_bytes, SNN_STAGE_ALL, &ro, stream, fdt);
+    RpnCall c = rpn_call(lv, fdt, n_levels, C, A, steps[n_steps - 1], p, w_shared_packed, w_heads_packed, out_logits, out_bbox, spike_counts, sum_logits,
+                         sum_bbox, ws, ws_bytes, stream);
+    c.steps = steps; c.n_steps = n_steps;
+    return rpn_head_run(c);
 }
 
 // ---- finished spike-rate tensors -------------------------------------------------------------------
@@ -2575,16 +2605,48 @@ static bool det_b3_tiles(const snn_params* p, const DetWindows& w) {
 // ... which takes its encoder planes word-major [T][D/32][R] (and hands fc6's spikes to fc7 that way)
 static bool det_planes_wm(const snn_params* p, const DetWindows& w) { return det_b3_tiles(p, w) && knobs().planes != 1; }
 
-// a detector pass with any-time readouts (snn_det_head_forward_readouts): outputs [n][R][K] / [n][R][K4], counts [n][R]
-struct DetReadouts { const int* steps; int n; uint32_t *c6, *c7; };
+// everything a detector head pass is told, whichever exported entry it came through (the entries check what is theirs alone - the step list,
+// the pairs that go together, the route - fill one of these and run it)
+struct DetCall {
+    bool roi_fed;                                              // the feed: rows of typed features x [R][D] (feed_rows) ...
+    const void* x; int D;
+    const snn_roi_level* levels_host; int n_levels, C;         // ... or RoIAlign over typed level maps, D = 49 C (feed_roialign)
+    const float* rois; const int *roi_batch, *roi_level;
+    int fdt, R, Hd, K, K4, T;                                  // T: the pass's last step
+    const snn_params* p;
+    const void* w6_packed; int w6_inner; const void* w7_packed; const float* w_heads_packed;
+    float *out_cls, *out_bbox; uint32_t *spk6_count, *spk7_count; float *sum_cls, *sum_bbox;
+    void* ws; size_t ws_bytes; snn_stream_t stream;
+    // any-time readouts (snn_det_head_forward_readouts): outputs [n][R][K] / [n][R][K4], counts [n][R]; null: one readout at T
+    const int* steps; int n_steps;
+    SparseRoute route;                                         // of fc6; .gated is the plan's to decide (DetPlan), not the entry's
+    const char* who;                                           // the name in messages: the feed's plain entry
+};
+// what every detector entry is told in the same words; the feed follows
+static DetCall det_call(int fdt, int R, int Hd, int K, int K4, int T, const snn_params* p, const void* w6_packed, int w6_inner,
+                        const void* w7_packed, const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
+                        uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
+    DetCall c = {};
+    c.fdt = fdt; c.R = R; c.Hd = Hd; c.K = K; c.K4 = K4; c.T = T; c.p = p;
+    c.w6_packed = w6_packed; c.w6_inner = w6_inner; c.w7_packed = w7_packed; c.w_heads_packed = w_heads_packed;
+    c.out_cls = out_cls; c.out_bbox = out_bbox; c.spk6_count = spk6_count; c.spk7_count = spk7_count; c.sum_cls = sum_cls; c.sum_bbox = sum_bbox;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+    c.route = SPARSE_ROUTE;
+    return c;
+}
+static void feed_rows(DetCall& c, const void* x, int D) { c.roi_fed = false; c.x = x; c.D = D; c.who = "snn_det_head_forward"; }
+static void feed_roialign(DetCall& c, const snn_roi_level* levels_host, int n_levels, int C, const float* rois, const int* roi_batch,
+                          const int* roi_level) {
+    c.roi_fed = true; c.levels_host = levels_host; c.n_levels = n_levels; c.C = C; c.rois = rois; c.roi_batch = roi_batch; c.roi_level = roi_level;
+    c.who = "snn_det_head_forward_roialign";
+}
 
 // the readout entry points' own checks, before those of the pass: the step list, then the arguments that go in pairs
-static int det_readouts(const char* who, const int* steps, int n, uint32_t* c6, uint32_t* c7, const float* sum_cls, const float* sum_bbox,
-                        DetReadouts* ro) {
+static int det_readouts_check(const char* who, const int* steps, int n, const uint32_t* c6, const uint32_t* c7, const float* sum_cls,
+                              const float* sum_bbox) {
     if (check_steps(steps, n, who)) return -1;
     if ((c6 == nullptr) != (c7 == nullptr)) return fail(-1, "%s: spk6_count and spk7_count go together", who);
     if ((sum_cls == nullptr) != (sum_bbox == nullptr)) return fail(-1, "%s: sum_cls and sum_bbox go together", who);
-    *ro = DetReadouts{steps, n, c6, c7};
     return 0;
 }
 
@@ -2595,86 +2657,86 @@ struct DetPlan {
     DetWindows win;
     bool wm, per;                        // encoder planes word-major (det_planes_wm); fc6 on the encoder's period planes (snn_common.h)
     bool bin_major;                      // an unfolded encoder already wrote RAW planes in fc6's bin-major order at o_enc (channels-last RoIAlign): no k_permute_planes
+    // fc6 route AUTO (snn_det_head_forward_routed): this call enqueues compress + count, the decision and both fc6 launches
+    // behind the gate word - where fc6's plan is the sparse launch on bin-major period planes and the call counts no spikes and reads out
+    // once; every other configuration runs its plan as it is.  The encoder then leaves every period plane raw (no fold)
+    bool gated;
 };
-static int det_plan(const char* who, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, bool spike_rates, bool wm_ok,
-                    size_t ws_bytes, DetPlan* dp) {
-    size_t need;
-    det_ws_layout(R, D, Hd, T, &dp->o_enc, &dp->o_cur, &dp->o_s6, &dp->o_s7, &need);
-    if (ws_bytes < need) return fail(-2, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    if (check_T(T, who)) return -1;
-    dp->o_raw = w6_inner > 1 ? det_ws_perm_offset(R, D, Hd, T) : dp->o_enc;
-    dp->bin_major = false;
-    dp->win = det_windows(p, T, spike_rates);
-    dp->wm = det_planes_wm(p, dp->win) && wm_ok;
-    dp->per = knobs().periods && periods_possible(p) && det_b3_tiles(p, dp->win);
-    return 0;
-}
 
 // will fc6 run the structured-sparse launch on the word-major period planes at o_enc?  fc6's own launcher is asked (nothing is enqueued)
-static bool det_fc6_sparse_plan(const DetPlan& dp, int R, int D, int Hd, int T, const snn_params* p, const void* w6_packed, uint32_t* spk6_count,
-                                void* ws, snn_stream_t stream) {
+static bool det_fc6_sparse_plan(const DetCall& c, int D, const DetPlan& dp) {
     Gemm3Args a6;
     G3Tile t6;
-    return spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)ws + dp.o_enc), T, R, D, Hd, p, (const uint16_t*)w6_packed,
-                                      (uint32_t*)((char*)ws + dp.o_s6), (size_t)R * cdiv(Hd, 32), spk6_count, true, true, &dp.win.fc6, true,
+    return spike_gemm_lif_bf16x3_args((const uint32_t*)((char*)c.ws + dp.o_enc), c.T, c.R, D, c.Hd, c.p, (const uint16_t*)c.w6_packed,
+                                      (uint32_t*)((char*)c.ws + dp.o_s6), (size_t)c.R * cdiv(c.Hd, 32), c.spk6_count, true, true, &dp.win.fc6, true,
                                       &a6, &t6) == 0 &&
-           gemm3_lif_sparse(a6, false, (char*)ws + dp.o_cur, dp.o_s6 - dp.o_cur, (hipStream_t)stream, SPARSE_QUERY) == 1;
+           gemm3_lif_sparse(a6, false, (char*)c.ws + dp.o_cur, dp.o_s6 - dp.o_cur, (hipStream_t)c.stream, SPARSE_QUERY, c.route, weight_planes(c.p)) == 1;
+}
+
+static int det_plan(const DetCall& c, int D, bool wm_ok, DetPlan* dp) {
+    size_t need;
+    det_ws_layout(c.R, D, c.Hd, c.T, &dp->o_enc, &dp->o_cur, &dp->o_s6, &dp->o_s7, &need);
+    if (c.ws_bytes < need) return fail(-2, "%s: workspace %zu < %zu bytes", c.who, c.ws_bytes, need);
+    if (check_T(c.T, c.who)) return -1;
+    dp->o_raw = c.w6_inner > 1 ? det_ws_perm_offset(c.R, D, c.Hd, c.T) : dp->o_enc;
+    dp->bin_major = false;
+    dp->win = det_windows(c.p, c.T, c.spk6_count != nullptr);
+    dp->wm = det_planes_wm(c.p, dp->win) && wm_ok;
+    dp->per = knobs().periods && periods_possible(c.p) && det_b3_tiles(c.p, dp->win);
+    dp->gated = c.route.route == SNN_ROUTE_AUTO && c.route.stat && !c.spk6_count && !c.steps && c.w6_inner == 49 && dp->wm && dp->per &&
+                det_fc6_sparse_plan(c, D, *dp);
+    return 0;
 }
 
 // rounds 5 / 6: where fc6 will run the structured-sparse launch on bin-major planes, ONE encoder launch writes them - permuted, e_3 ..
 // compressed - instead of encoder + k_permute_planes + k_compress_planes.  fc6's own launcher is asked (nothing is enqueued).  feed_ok:
 // the feed's own conditions; *np, *eth: the folded encoder's neuron and threshold table
-static bool det_fc6_folds(bool feed_ok, const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
-                          uint32_t* spk6_count, void* ws, snn_stream_t stream, NeuronP* np, const EncTh** eth) {
-    if (g_fc6_route.gated || !knobs().enc_fold || !feed_ok || w6_inner != 49 || !dp.wm || !dp.per) return false;      // (the gated fc6 route reads raw planes)
-    *np = make_p(p, p->v_th_enc);
+static bool det_fc6_folds(bool feed_ok, const DetCall& c, int D, const DetPlan& dp, NeuronP* np, const EncTh** eth) {
+    if (dp.gated || !knobs().enc_fold || !feed_ok || c.w6_inner != 49 || !dp.wm || !dp.per) return false;      // (the gated fc6 route reads raw planes)
+    *np = make_p(c.p, c.p->v_th_enc);
     np->v_fire = ENC_FIRED;
     if (!enc_zero_rest(*np) || enc_mode(*np, eth) != ENC_QUANT) return false;
-    return det_fc6_sparse_plan(dp, R, D, Hd, T, p, w6_packed, spk6_count, ws, stream);
-}
-
-// fc6 route AUTO (snn_det_head_forward_routed): does this call enqueue compress + count, the decision and both fc6 launches
-// behind the gate word?  Where fc6's plan is the sparse launch on bin-major period planes and the call counts no spikes and reads out once;
-// every other configuration runs its plan as it is.  The encoder then leaves every period plane raw (no fold)
-static bool det_fc6_gated(const DetPlan& dp, int R, int D, int Hd, int T, int w6_inner, const snn_params* p, const void* w6_packed,
-                          uint32_t* spk6_count, void* ws, snn_stream_t stream, const DetReadouts* ro) {
-    if (g_fc6_route.route != SNN_ROUTE_AUTO || !g_fc6_route.stat || spk6_count || ro || w6_inner != 49 || !dp.wm || !dp.per) return false;
-    return det_fc6_sparse_plan(dp, R, D, Hd, T, p, w6_packed, spk6_count, ws, stream);
+    return det_fc6_sparse_plan(c, D, dp);
 }
 
 // the LI heads at the end of a detector pass: one readout at T (the plain forward), or the readout set with its spike counts
-static int det_heads_tail(const uint32_t* s6, const uint32_t* s7, int R, int Hd, int K, int K4, int T, const snn_params* p, const float* w_heads_packed,
-                          float* out_cls, float* out_bbox, float* sum_cls, float* sum_bbox, bool s6_wm, const DetReadouts* ro, snn_stream_t stream) {
-    const int Hw = cdiv(Hd, 32);
-    if (!ro) return snn_li_heads(s7, (size_t)R * Hw, T, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls, sum_bbox, stream);
-    int rc = li_heads_readouts_impl(s7, (size_t)R * Hw, ro->steps, ro->n, R, Hd, w_heads_packed, K, K4, p, out_cls, out_bbox, sum_cls, sum_bbox,
-                                    false, stream);
-    if (rc || !ro->c6) return rc;
-    const StepList st = step_list(ro->steps, ro->n);
-    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, s6, (unsigned long long)R * Hw, R, Hw, s6_wm ? 1 : 0, st, ro->c6);
+static int det_heads_tail(const DetCall& c, const uint32_t* s6, const uint32_t* s7, bool s6_wm) {
+    const int R = c.R, Hw = cdiv(c.Hd, 32);
+    if (!c.steps)
+        return snn_li_heads(s7, (size_t)R * Hw, c.T, R, c.Hd, c.w_heads_packed, c.K, c.K4, c.p, c.out_cls, c.out_bbox, c.sum_cls, c.sum_bbox, c.stream);
+    int rc = li_heads_readouts_impl(s7, (size_t)R * Hw, c.steps, c.n_steps, R, c.Hd, c.w_heads_packed, c.K, c.K4, c.p, c.out_cls, c.out_bbox, c.sum_cls,
+                                    c.sum_bbox, false, c.stream);
+    if (rc || !c.spk6_count) return rc;
+    const StepList st = step_list(c.steps, c.n_steps);
+    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)c.stream, s6, (unsigned long long)R * Hw, R, Hw, s6_wm ? 1 : 0, st, c.spk6_count);
     SNN_CHECK_LAUNCH("k_count_rows_ro");
-    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, s7, (unsigned long long)R * Hw, R, Hw, 0, st, ro->c7);
+    hipLaunchKernelGGL(k_count_rows_ro, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)c.stream, s7, (unsigned long long)R * Hw, R, Hw, 0, st, c.spk7_count);
     SNN_CHECK_LAUNCH("k_count_rows_ro");
     return 0;
 }
 
 // route_stat of a routed detector call that did not decide on the device: {0, 0, 0 = the sparse fc6 launch ran (and always in spike-rate
 // mode) / 1 = dense, 0}; nothing on every other entry
-static int fc6_route_fixed(int route_taken, hipStream_t s) {
-    if (!g_fc6_route.stat) return 0;
-    hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)g_fc6_route.stat, (const int*)nullptr, 0, 0, 0.0f, route_taken);
+static int fc6_route_fixed(int32_t* route_stat, int route_taken, hipStream_t s) {
+    if (!route_stat) return 0;
+    hipLaunchKernelGGL(k_route_decide, dim3(1), dim3(64), 0, s, (int*)route_stat, (const int*)nullptr, 0, 0, 0.0f, route_taken);
     SNN_CHECK_LAUNCH("k_route_decide");
     return 0;
 }
 
-static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, const snn_params* p, const void* w6_packed,
-                                const void* w7_packed, const float* w_heads_packed, float* out_cls, float* out_bbox,
-                                uint32_t* spk6_count, uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws,
-                                const DetPlan& dp, snn_stream_t stream, int k_inner, bool folded, const DetReadouts* ro) {
+// the pass behind its encoder launch, whichever feed wrote the planes: fc6 + LIF, fc7 + LIF, the LI heads
+static int det_head_from_planes(const DetCall& c, int D, const DetPlan& dp, bool folded) {
     // folded (round 5): the encoder launch already wrote the planes in fc6's permuted order, e_3 .. compressed (k_encode_rows_perm): no
     // k_permute_planes, no k_compress_planes - fc6 must then run the structured-sparse launch (it was asked beforehand)
+    const int R = c.R, Hd = c.Hd, T = c.T, k_inner = c.w6_inner, planes = weight_planes(c.p);
+    const snn_params* const p = c.p;
+    const void *const w6_packed = c.w6_packed, *const w7_packed = c.w7_packed;
+    uint32_t *const spk6_count = c.spk6_count, *const spk7_count = c.spk7_count;
+    void* const ws = c.ws;
+    const snn_stream_t stream = c.stream;
     const size_t o_enc = dp.o_enc, o_cur = dp.o_cur, o_s6 = dp.o_s6, o_s7 = dp.o_s7;
-    const WeightPlanesScope planes(p);
+    SparseRoute rt = c.route;
+    rt.gated = dp.gated;
     const DetWindows& win = dp.win;
     const bool enc_wm = dp.wm, enc_periods = dp.per;
     hipStream_t s = (hipStream_t)stream;
@@ -2708,10 +2770,10 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
             return fail(-4, "snn_det_head_forward: the mxfp6 kernels need D, Hd %% 128 == 0");
         // (spike-rate mode: per-RoI counts come out of the LIF epilogues)
         if (!mx_tile_ok(win.fc6.n) || !mx_tile_ok(win.fc7.n)) return fail(-4, "snn_det_head_forward: T=%d does not fit a 512-row tile of the mxfp6 kernels", T);
-        if ((rc = fc6_route_fixed(spk6_count ? 0 : 1, s))) return rc;
+        if ((rc = fc6_route_fixed(rt.stat, spk6_count ? 0 : 1, s))) return rc;
         if ((rc = spike_gemm_lif_mx_impl(enc, T, R, D, Hd, p, (const uint32_t*)w6_packed, s6, (size_t)R * Hw, spk6_count, stream, &win.fc6))) return rc;
         if ((rc = spike_gemm_lif_mx_impl(s6, T, R, Hd, Hd, p, (const uint32_t*)w7_packed, s7, (size_t)R * Hw, spk7_count, stream, &win.fc7))) return rc;
-        return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, false, ro, stream);
+        return det_heads_tail(c, s6, s7, false);
     }
     if ((enc_wm || enc_periods) && !det_b3_tiles(p, win)) return fail(-1, "snn_det_head_forward: word-major / period planes without the fused bf16x3 layers");
     if (det_b3_tiles(p, win)) {
@@ -2727,53 +2789,40 @@ static int det_head_from_planes(int R, int D, int Hd, int K, int K4, int T, cons
         const int wn = g3_wn();
         // round 4: fc6's sparse period planes e_3 .. on the structured-sparse matrix-core instruction (snn_sparse.h); its side buffers
         // live in the currents region of the workspace, which the fused layers never write
-        rc = gemm3_lif_sparse(a6, false, (char*)ws + o_cur, o_s6 - o_cur, s, folded ? SPARSE_RUN_COMPRESSED : SPARSE_RUN);
-        const bool was_gated = g_fc6_route.gated;
-        g_fc6_route.gated = false;
+        rc = gemm3_lif_sparse(a6, false, (char*)ws + o_cur, o_s6 - o_cur, s, folded ? SPARSE_RUN_COMPRESSED : SPARSE_RUN, rt, planes);
         if (rc < 0) return rc;
         if (folded && rc != 1) return fail(-3, "snn_det_head_forward: the encoder wrote compressed planes but fc6 takes the dense launch (internal)");
-        if (was_gated && rc != 2) return fail(-3, "snn_det_head_forward: fc6 route: the gated pair was planned but fc6 did not enqueue it (internal)");
+        if (rt.gated && rc != 2) return fail(-3, "snn_det_head_forward: fc6 route: the gated pair was planned but fc6 did not enqueue it (internal)");
         g_last_fc_sparse = rc;
-        if (rc == 2) { a6.gate = (const int*)g_fc6_route.stat + 2; a6.gate_want = 1; }      // the gated route: the dense launch on the same raw planes and weights, behind the same word
-        else if ((rc = fc6_route_fixed((spk6_count || rc == 1) ? 0 : 1, s))) return rc;
-        if (g_last_fc_sparse != 1 && (rc = launch_gemm3(G3_FC_LIF_TILE, t6.mt, wn, a6, s))) return rc;
-        if ((rc = launch_gemm3(G3_FC_LIF_TILE, t7.mt, wn, a7, s))) return rc;
-        return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, enc_wm, ro, stream);
+        if (rc == 2) { a6.gate = (const int*)rt.stat + 2; a6.gate_want = 1; }      // the gated route: the dense launch on the same raw planes and weights, behind the same word
+        else if ((rc = fc6_route_fixed(rt.stat, (spk6_count || rc == 1) ? 0 : 1, s))) return rc;
+        if (g_last_fc_sparse != 1 && (rc = launch_gemm3(G3_FC_LIF_TILE, t6.mt, wn, a6, planes, s))) return rc;
+        if ((rc = launch_gemm3(G3_FC_LIF_TILE, t7.mt, wn, a7, planes, s))) return rc;
+        return det_heads_tail(c, s6, s7, enc_wm);
     }
     // fc6 for all (live) time steps at once: rows m = (t - t0)*R + r   (faster_rcnn.py:498)
-    if ((rc = fc6_route_fixed(spk6_count ? 0 : 1, s))) return rc;
+    if ((rc = fc6_route_fixed(rt.stat, spk6_count ? 0 : 1, s))) return rc;
     const uint32_t* a6 = enc + (size_t)win.fc6.t0 * R * cdiv(D, 32);
-    rc = b3 ? snn_spike_gemm_bf16x3(a6, win.fc6.n * R, D, Hd, (const uint16_t*)w6_packed, cur, Hp, stream)
+    rc = b3 ? spike_gemm_bf16x3_impl(a6, win.fc6.n * R, D, Hd, (const uint16_t*)w6_packed, cur, Hp, planes, stream)
             : snn_spike_gemm(a6, win.fc6.n * R, D, Hd, (const float*)w6_packed, cur, Hp, stream);
     if (rc) return rc;
     if ((rc = lif_scan_window(cur, T, win.fc6, R, Hd, Hp, p, s6, (size_t)R * Hw, spk6_count, stream))) return rc;   // :499
     const uint32_t* a7 = s6 + (size_t)win.fc7.t0 * R * Hw;
-    rc = b3 ? snn_spike_gemm_bf16x3(a7, win.fc7.n * R, Hd, Hd, (const uint16_t*)w7_packed, cur, Hp, stream)
+    rc = b3 ? spike_gemm_bf16x3_impl(a7, win.fc7.n * R, Hd, Hd, (const uint16_t*)w7_packed, cur, Hp, planes, stream)
             : snn_spike_gemm(a7, win.fc7.n * R, Hd, Hd, (const float*)w7_packed, cur, Hp, stream);                       // :500
     if (rc) return rc;
     if ((rc = lif_scan_window(cur, T, win.fc7, R, Hd, Hp, p, s7, (size_t)R * Hw, spk7_count, stream))) return rc;   // :501
-    return det_heads_tail(s6, s7, R, Hd, K, K4, T, p, w_heads_packed, out_cls, out_bbox, sum_cls, sum_bbox, false, ro,
-                          stream);                                                                       // :505-510
+    return det_heads_tail(c, s6, s7, false);                                                             // :505-510
 }
 
-static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
-                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
-                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
-                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream, const DetReadouts* ro) {
-    if (!x || !p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
-        return fail(-1, "snn_det_head_forward: null argument");
-    if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward: bad shape");
-    if (check_T(T, "snn_det_head_forward")) return -1;          // (the row-fed entry points check T before the workspace)
-    if (check_feat_rows(x, fdt, "snn_det_head_forward")) return -1;
-    DetPlan dp;
-    int rc;
-    if ((rc = det_plan("snn_det_head_forward", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, encode_rows_wm_ok(x, D), ws_bytes, &dp)))
-        return rc;
-    if (w6_inner > 1 && !dp.wm) return fail(-4, "snn_det_head_forward: permuted fc6 weights need the word-major fused bf16x3 path (D %% 32 == 0, x 16-byte aligned)");
+// the rows feed behind the plan: what it asks of the plan, then its encoder launch - folded (k_encode_rows_perm) or encode_rows_impl
+static int det_encode_rows(const DetCall& c, const DetPlan& dp, bool* folded) {
+    const void* const x = c.x;
+    const int R = c.R, D = c.D;
+    if (c.w6_inner > 1 && !dp.wm) return fail(-4, "snn_det_head_forward: permuted fc6 weights need the word-major fused bf16x3 path (D %% 32 == 0, x 16-byte aligned)");
     NeuronP np;
     const EncTh* eth_f = nullptr;
-    g_fc6_route.gated = det_fc6_gated(dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, ro);      // (the entry's scope clears it on every early return)
-    const bool fold = det_fc6_folds(D % (49 * 64) == 0, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
+    const bool fold = *folded = det_fc6_folds(D % (49 * 64) == 0, c, D, dp, &np, &eth_f);
     if (fold) {
         const int Te = dp.win.enc_steps, C = D / 49;
         const int rb = knobs().encp_rb ? (knobs().encp_rb == 16 ? 16 : 8) : (Te <= ENCP_LDS_WORDS / (2 * 49 * 16) ? 16 : 8);     // (one pass through LDS where 16 RoIs per block allow it)
@@ -2781,39 +2830,29 @@ static int det_head_forward_impl(const void* x, int fdt, int R, int D, int Hd, i
         // eight waves per block where only two blocks fit a CU's LDS (T_det = 12: -2 us, T_det = 24: -10 us), four where three fit (T_det = 16: eight
         // were 9 us slower) - profiles/r5_encoder_nw_ab.txt
         const int nw = knobs().encp_nw ? (knobs().encp_nw == 4 ? 4 : 8) : (lds > 53 * 1024 ? 8 : 4);
-        const void* kern = encode_rows_perm_kernel(rb, nw, fdt);
+        const void* kern = encode_rows_perm_kernel(rb, nw, c.fdt);
         g_last_enc_mode = ENC_QUANT;                            // (det_fc6_folds: the folded encoder exists in the threshold form only)
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(-3, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        uint32_t* planes_f = (uint32_t*)((char*)ws + dp.o_enc);
-        uint32_t* cmp_f = (uint32_t*)((char*)ws + dp.o_cur);
+        uint32_t* planes_f = (uint32_t*)((char*)c.ws + dp.o_enc);
+        uint32_t* cmp_f = (uint32_t*)((char*)c.ws + dp.o_cur);
         const int nd_f = 2;
         void* kargs[] = {(void*)&x, (void*)&R, (void*)&C, (void*)&Te, (void*)&nd_f, (void*)eth_f, (void*)&planes_f, (void*)&cmp_f};
-        e = hipLaunchKernel(kern, dim3(cdiv(R, rb), C / 64), dim3(64 * nw), kargs, lds, (hipStream_t)stream);
+        e = hipLaunchKernel(kern, dim3(cdiv(R, rb), C / 64), dim3(64 * nw), kargs, lds, (hipStream_t)c.stream);
         if (e != hipSuccess) return fail(-3, "k_encode_rows_perm launch failed: %s", hipGetErrorString(e));
         SNN_CHECK_LAUNCH("k_encode_rows_perm");
-    } else if ((rc = encode_rows_impl(x, R, D, dp.win.enc_steps, p, (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), dp.wm, stream,
-                                      dp.per, fdt))) {
-        return rc;                                              // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
+        return 0;
     }
-    return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
+    // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
+    return encode_rows_impl(x, R, D, dp.win.enc_steps, c.p, (uint32_t*)((char*)c.ws + dp.o_raw), (size_t)R * cdiv(D, 32), dp.wm, c.stream, dp.per, c.fdt);
 }
 
-static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
-                                          const int* roi_batch, const int* roi_level, int R, int Hd, int K, int K4, int T,
-                                          const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
-                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
-                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
-                                          snn_stream_t stream, const DetReadouts* ro) {
-    if (!p || !w6_packed || !w7_packed || !w_heads_packed || !out_cls || !out_bbox || !ws)
-        return fail(-1, "snn_det_head_forward_roialign: null argument");
-    if (R <= 0 || C <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_forward_roialign: bad shape");
-    const int D = C * 49;
-    DetPlan dp;
-    int rc;
-    if ((rc = det_plan("snn_det_head_forward_roialign", R, D, Hd, T, w6_inner, p, spk6_count != nullptr, true, ws_bytes, &dp))) return rc;
-    if (w6_inner > 1 && (!dp.wm || w6_inner != 49)) return fail(-4, "snn_det_head_forward_roialign: permuted fc6 weights need inner = 49 and the word-major fused bf16x3 path");
+// the RoIAlign feed behind the plan: what it asks of the plan and of its maps, then its encoder launch - k_roi_align_encode_perm (folded, or
+// channels-last maps) or roi_align_encode_impl
+static int det_encode_roialign(const DetCall& c, int D, DetPlan& dp, bool* folded) {
+    const snn_roi_level* const levels_host = c.levels_host;
+    const int fdt = c.fdt, n_levels = c.n_levels, C = c.C, R = c.R;
+    if (c.w6_inner > 1 && (!dp.wm || c.w6_inner != 49)) return fail(-4, "snn_det_head_forward_roialign: permuted fc6 weights need inner = 49 and the word-major fused bf16x3 path");
     // the feature dtype / layout code and every level's base pointer, once, before anything is asked of fc6 or enqueued
     if (check_feat(nullptr, fdt, "snn_det_head_forward_roialign")) return -1;
     for (int l = 0; levels_host && n_levels <= 4 && l < n_levels; ++l)
@@ -2823,22 +2862,21 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
     // head takes 0.943 against 0.948 ms at T_det = 12 - the launch itself is 30 us slower than the table kernel (7 of 8 lanes per bin row, a second
     // pass that transposes the ballots) and saves k_permute_planes + k_compress_planes (38 us) and their two 31-MB plane copies - but 2.04 against
     // 1.88 ms at T_det = 24, where its 44 KB of LDS leave three work-groups per CU to a launch that lives on loads in flight.
-    bool feed_geo = knobs().roi_tab && C % 64 == 0 && levels_host && rois && roi_batch && roi_level && n_levels > 0 && n_levels <= 4;
+    bool feed_geo = knobs().roi_tab && C % 64 == 0 && levels_host && c.rois && c.roi_batch && c.roi_level && n_levels > 0 && n_levels <= 4;
     for (int l = 0; l < n_levels && feed_geo; ++l)
         feed_geo = levels_host[l].feat && levels_host[l].H > 0 && levels_host[l].W >= 2 && (long long)C * levels_host[l].H * levels_host[l].W < (1ll << 29);
     const bool feed_ok = feed_geo && dp.win.enc_steps <= 12;
     NeuronP np;
     const EncTh* eth_f = nullptr;
-    g_fc6_route.gated = det_fc6_gated(dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, ro);      // (the entry's scope clears it on every early return)
-    const bool fold = det_fc6_folds(feed_ok, dp, R, D, Hd, T, w6_inner, p, w6_packed, spk6_count, ws, stream, &np, &eth_f);
+    const bool fold = *folded = det_fc6_folds(feed_ok, c, D, dp, &np, &eth_f);
     // channels-last maps (SNN_FEAT_NHWC): one kernel, for the plans in which fc6 reads bin-major period planes - folded as above, or (longer windows,
     // a dense fc6) every plane raw in bin-major order where k_permute_planes would have put it, k_compress_planes following as before
     const bool nhwc = (fdt & SNN_FEAT_NHWC) != 0;
     bool nhwc_raw = false;
     if (nhwc && !fold) {
-        nhwc_raw = feed_geo && w6_inner == 49 && dp.wm && dp.per;
+        nhwc_raw = feed_geo && c.w6_inner == 49 && dp.wm && dp.per;
         if (nhwc_raw) {
-            np = make_p(p, p->v_th_enc);
+            np = make_p(c.p, c.p->v_th_enc);
             np.v_fire = ENC_FIRED;
             nhwc_raw = enc_zero_rest(np) && enc_mode(np, &eth_f) == ENC_QUANT;
         }
@@ -2852,23 +2890,38 @@ static int det_head_forward_roialign_impl(const snn_roi_level* levels_host, int 
             fa.lv[l].feat = levels_host[l].feat; fa.lv[l].H = levels_host[l].H; fa.lv[l].W = levels_host[l].W; fa.lv[l].scale = levels_host[l].spatial_scale;
         }
         fa.p = np; fa.quant = 1; fa.eth = *eth_f;
-        fa.rois = rois; fa.roi_batch = roi_batch; fa.roi_level = roi_level;
-        fa.planes = (uint32_t*)((char*)ws + dp.o_enc); fa.cmp = fold ? (uint32_t*)((char*)ws + dp.o_cur) : nullptr; fa.nd = 2;
+        fa.rois = c.rois; fa.roi_batch = c.roi_batch; fa.roi_level = c.roi_level;
+        fa.planes = (uint32_t*)((char*)c.ws + dp.o_enc); fa.cmp = fold ? (uint32_t*)((char*)c.ws + dp.o_cur) : nullptr; fa.nd = 2;
         fa.plane_stride = (unsigned long long)R * cdiv(D, 32); fa.R = R; fa.C = C; fa.T = dp.win.enc_steps; fa.Dw = cdiv(D, 32);
         fa.RW = RW; fa.n_rg = cdiv(R, 4 * RW);
         const int n_cp = C / 64, n_items = fa.n_rg * 7;
         const int grid = (8 % n_cp == 0) ? 8 * cdiv(n_items, 8 / n_cp) : n_cp * n_items;
         const size_t lds = (size_t)fa.T * (nhwc ? 7 : 7 + 8) * 4 * RW * 8;       // word pairs + raw ballots (channels-last: word pairs only)
         g_last_enc_mode = ENC_QUANT;
-        launch_picked(roi_align_encode_perm_kernel<RW>(fdt), dim3(grid), dim3(256), lds, (hipStream_t)stream, fa);
+        launch_picked(roi_align_encode_perm_kernel<RW>(fdt), dim3(grid), dim3(256), lds, (hipStream_t)c.stream, fa);
         SNN_CHECK_LAUNCH("k_roi_align_encode_perm");
         dp.bin_major = nhwc_raw;
-    } else if ((rc = roi_align_encode_impl(levels_host, n_levels, C, rois, roi_batch, roi_level, R, dp.win.enc_steps, p,
-                                           (uint32_t*)((char*)ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, stream, dp.per, fdt))) {
-        return rc;                                              // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
+        return 0;
     }
-    return det_head_from_planes(R, D, Hd, K, K4, T, p, w6_packed, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                spk6_count, spk7_count, sum_cls, sum_bbox, ws, dp, stream, w6_inner, fold, ro);
+    // (SNN_STATUS_NO_TYPED_KERNEL included: nothing has been enqueued)
+    return roi_align_encode_impl(levels_host, n_levels, C, c.rois, c.roi_batch, c.roi_level, R, dp.win.enc_steps, c.p,
+                                 (uint32_t*)((char*)c.ws + dp.o_raw), (size_t)R * cdiv(D, 32), nullptr, dp.wm, c.stream, dp.per, fdt);
+}
+
+// the detector head: the checks and the plan both feeds share, the feed's encoder launch, then fc6, fc7 and the LI heads
+static int det_head_run(const DetCall& c) {
+    if ((!c.roi_fed && !c.x) || !c.p || !c.w6_packed || !c.w7_packed || !c.w_heads_packed || !c.out_cls || !c.out_bbox || !c.ws)
+        return fail(-1, "%s: null argument", c.who);
+    if (c.R <= 0 || (c.roi_fed ? c.C : c.D) <= 0 || c.Hd <= 0 || c.K <= 0 || c.K4 <= 0) return fail(-1, "%s: bad shape", c.who);
+    const int D = c.roi_fed ? c.C * 49 : c.D;
+    // (the row-fed entry points check T before the workspace, and their feature code before the plan)
+    if (!c.roi_fed && (check_T(c.T, c.who) || check_feat_rows(c.x, c.fdt, c.who))) return -1;
+    DetPlan dp;
+    int rc;
+    if ((rc = det_plan(c, D, c.roi_fed || encode_rows_wm_ok(c.x, D), &dp))) return rc;
+    bool folded = false;
+    if ((rc = c.roi_fed ? det_encode_roialign(c, D, dp, &folded) : det_encode_rows(c, dp, &folded))) return rc;
+    return det_head_from_planes(c, D, dp, folded);
 }
 
 int snn_det_head_forward(const float* x, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
@@ -2891,8 +2944,10 @@ int snn_det_head_forward_k_typed(const void* x, int fdt, int R, int D, int Hd, i
                                  const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                                  float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                                  float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
-                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+    DetCall c = det_call(fdt, R, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_rows(c, x, D);
+    return det_head_run(c);
 }
 
 // spike-rate readouts: the pass runs as a spike-rate forward at T (same launches, windows of every lif6 step); its per-RoI counts land in
@@ -2909,10 +2964,12 @@ int snn_det_head_forward_readouts_typed(const void* x, int fdt, int R, int D, in
                                         const snn_params* p, const void* w6_packed, int w6_inner, const void* w7_packed,
                                         const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                         uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, snn_stream_t stream) {
-    DetReadouts ro;
-    if (det_readouts("snn_det_head_forward_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
-    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox,
-                                 spk6_count, spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, &ro);
+    if (det_readouts_check("snn_det_head_forward_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox)) return -1;
+    DetCall c = det_call(fdt, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_rows(c, x, D);
+    c.steps = steps; c.n_steps = n_steps;
+    return det_head_run(c);
 }
 
 int snn_det_head_forward_roialign(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
@@ -2943,9 +3000,10 @@ int snn_det_head_forward_roialign_k_typed(const snn_roi_level* levels_host, int 
                                           const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                           uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                           snn_stream_t stream) {
-    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
-                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
-                                          ws_bytes, stream, nullptr);
+    DetCall c = det_call(fdt, R, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_roialign(c, levels_host, n_levels, C, rois, roi_batch, roi_level);
+    return det_head_run(c);
 }
 
 int snn_det_head_forward_roialign_readouts(const snn_roi_level* levels_host, int n_levels, int C, const float* rois,
@@ -2965,44 +3023,35 @@ int snn_det_head_forward_roialign_readouts_typed(const snn_roi_level* levels_hos
                                                  const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                                  uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                                  snn_stream_t stream) {
-    DetReadouts ro;
-    if (det_readouts("snn_det_head_forward_roialign_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox, &ro)) return -1;
-    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed,
-                                          w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
-                                          ws_bytes, stream, &ro);
+    if (det_readouts_check("snn_det_head_forward_roialign_readouts", steps, n_steps, spk6_count, spk7_count, sum_cls, sum_bbox)) return -1;
+    DetCall c = det_call(fdt, R, Hd, K, K4, steps[n_steps - 1], p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_roialign(c, levels_host, n_levels, C, rois, roi_batch, roi_level);
+    c.steps = steps; c.n_steps = n_steps;
+    return det_head_run(c);
 }
 
 // ---- fc6 route of the detector head ----
 // the routed forward's workspace: the plain forward's.  Its front region holds the raw bin-major planes of every period, the currents region the
 // compressed planes and the hit counters; the gate word is route_stat[2], in the caller's array
-static bool route_known(int route) { return route == SNN_ROUTE_SPARSE || route == SNN_ROUTE_DENSE || route == SNN_ROUTE_AUTO; }
 size_t snn_det_head_workspace_bytes_routed(int R, int D, int Hd, int K, int K4, int T, int precision, int route) {
     if (!route_known(route)) return 0;
     return snn_det_head_workspace_bytes(R, D, Hd, K, K4, T, precision);
 }
 
-// the checks the two routed entries share, before anything is asked of the plan or enqueued
-static int det_route_check(const char* who, int R, int D, int Hd, int K, int K4, int T, const snn_params* p, size_t ws_bytes, int route,
-                           float crossover, const int32_t* route_stat) {
-    if (!route_known(route)) return fail(-1, "%s: unknown route %d", who, route);
-    if (route == SNN_ROUTE_AUTO && !route_stat) return fail(-1, "%s: SNN_ROUTE_AUTO needs route_stat", who);
-    if (route == SNN_ROUTE_AUTO && crossover != crossover) return fail(-1, "%s: crossover is not a number", who);
-    if (p && R > 0 && D > 0 && Hd > 0 && T >= 1) {              // (anything else: the forward's own message)
-        const size_t need = snn_det_head_workspace_bytes_routed(R, D, Hd, K, K4, T, p->precision, route);
-        if (ws_bytes < need) return fail(-1, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    }
-    return 0;
-}
 
 int snn_det_head_forward_routed(const void* x, int fdt, int R, int D, int Hd, int K, int K4, int T, const snn_params* p,
                                 const void* w6_packed, int w6_inner, const void* w7_packed, const float* w_heads_packed,
                                 float* out_cls, float* out_bbox, uint32_t* spk6_count, uint32_t* spk7_count,
                                 float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes, int route, float crossover,
                                 int32_t* route_stat, snn_stream_t stream) {
-    if (det_route_check("snn_det_head_forward_routed", R, D, Hd, K, K4, T, p, ws_bytes, route, crossover, route_stat)) return -1;
-    const Fc6RouteScope scope(spk6_count ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);      // (spike-rate mode: the plain plan on every route)
-    return det_head_forward_impl(x, fdt, R, D, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count,
-                                 spk7_count, sum_cls, sum_bbox, ws, ws_bytes, stream, nullptr);
+    const size_t need = p ? snn_det_head_workspace_bytes_routed(R, D, Hd, K, K4, T, p->precision, route) : 0;      // (no p: the pass's own message)
+    if (route_check("snn_det_head_forward_routed", route, crossover, route_stat, ws_bytes, need)) return -1;
+    DetCall c = det_call(fdt, R, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_rows(c, x, D);
+    c.route = routed(route, crossover, route_stat, spk6_count != nullptr);
+    return det_head_run(c);
 }
 
 int snn_det_head_forward_roialign_routed(const snn_roi_level* levels_host, int fdt, int n_levels, int C, const float* rois,
@@ -3011,13 +3060,13 @@ int snn_det_head_forward_roialign_routed(const snn_roi_level* levels_host, int f
                                          const float* w_heads_packed, float* out_cls, float* out_bbox, uint32_t* spk6_count,
                                          uint32_t* spk7_count, float* sum_cls, float* sum_bbox, void* ws, size_t ws_bytes,
                                          int route, float crossover, int32_t* route_stat, snn_stream_t stream) {
-    if (det_route_check("snn_det_head_forward_roialign_routed", R, C > 0 && C < (1 << 24) ? C * 49 : 0, Hd, K, K4, T, p, ws_bytes, route, crossover,
-                        route_stat))
-        return -1;
-    const Fc6RouteScope scope(spk6_count ? (int)SNN_ROUTE_SPARSE : route, crossover, route_stat);
-    return det_head_forward_roialign_impl(levels_host, fdt, n_levels, C, rois, roi_batch, roi_level, R, Hd, K, K4, T, p, w6_packed, w6_inner,
-                                          w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls, sum_bbox, ws,
-                                          ws_bytes, stream, nullptr);
+    const size_t need = p ? snn_det_head_workspace_bytes_routed(R, C > 0 && C < (1 << 24) ? C * 49 : 0, Hd, K, K4, T, p->precision, route) : 0;
+    if (route_check("snn_det_head_forward_roialign_routed", route, crossover, route_stat, ws_bytes, need)) return -1;
+    DetCall c = det_call(fdt, R, Hd, K, K4, T, p, w6_packed, w6_inner, w7_packed, w_heads_packed, out_cls, out_bbox, spk6_count, spk7_count, sum_cls,
+                         sum_bbox, ws, ws_bytes, stream);
+    feed_roialign(c, levels_host, n_levels, C, rois, roi_batch, roi_level);
+    c.route = routed(route, crossover, route_stat, spk6_count != nullptr);
+    return det_head_run(c);
 }
 
 int snn_det_exchange_payload(const float* class_logits, const float* box_regression, int N, int rois_per_image, int K,
