@@ -17,8 +17,21 @@
  * Conventions
  *   - every pointer is a DEVICE pointer unless it says "host"; the caller owns every buffer; the
  *     library allocates nothing persistent and frees nothing of the caller's;
- *   - all work is enqueued on the stream passed in; no internal synchronisation, no default-stream
- *     use, no host<->device copies: every call is hipGraph-capturable;
+ *   - all work is enqueued on the stream passed in; no default-stream use.  With three exceptions no call synchronises,
+ *     allocates, frees or copies between host and device, so every other call is hipGraph-capturable.  The exceptions are
+ *     the bf16 packers snn_pack_conv3x3_weight_bf16, snn_pack_linear_weight_bf16 and snn_pack_linear_weight_bf16_perm:
+ *     they allocate a status word, copy the verdict (a weight that is not finite or rounds to +-inf) to the host, wait for
+ *     the stream and free the word.  Call them before a capture, never inside one;
+ *   - capture contract of every other call: ONE stream (no fork / join inside the capture); warm caches on the caller's
+ *     side (packed weights and whatever else the binding builds lazily exist before the capture begins: call once eagerly
+ *     first); and every buffer the call was handed - operands, outputs, workspace, route_stat, count tensors - lives as
+ *     long as the graph, which reads and writes the same addresses on every replay.  The launch attributes and occupancy
+ *     queries a call makes on the host are accepted while its stream is capturing.  Nothing a call decides on the host
+ *     depends on the contents of a device buffer, and every counter a call uses is cleared by work of that call on the
+ *     stream, so a replay on new contents returns what an eager call on them returns, bit for bit
+ *     (tests/test_gpu_graph_capture.py; tests/test_graph_capture_cpu.py pins the list of exceptions to csrc/).  One
+ *     configuration is NOT established: the *_routed heads in route "auto" at C = 256 / Hd = 1024 inside a capture of
+ *     the five-call static-shape sequence ("Graph capture": open);
  *   - return value 0 = success, negative = error (message via snn_last_error(), thread-local);
  *     no exceptions cross the ABI and the library never aborts;
  *   - re-entrant: no global mutable state besides the thread-local error string.  Two kinds of process-wide constants are
@@ -407,7 +420,7 @@ int snn_pack_linear_weight_bf16x3(const float* w_nk, int N, int K, uint16_t* pac
  * kept: bit for bit torch's w.to(torch.bfloat16)) - the *_elems counts are a third of the bf16x3 ones.  The _perm form packs fc6 in bin-major order
  * as snn_pack_linear_weight_bf16x3_perm does.  A tensor with a non-finite weight or one that rounds to +-inf is REFUSED: the call returns -4
  * (snn_last_error) - there is no other precision that computes the same thing to fall back to.  To deliver that verdict these three calls wait
- * for the stream (pack time only).  Bad arguments return -1 before any device work.
+ * for the stream (pack time only) and are NOT hipGraph-capturable (Conventions).  Bad arguments return -1 before any device work.
  * The LI heads have NO packer of their own at this precision: they keep snn_pack_heads_weight and its layout, and the CALLER rounds the two
  * head weight matrices to bf16 (ties to even) and back to fp32 before that call, and refuses non-finite results itself - as the Python
  * binding's ops.pack_heads_bf16 does.  Head weights passed unrounded run unrounded: the result is then not this mode's. */

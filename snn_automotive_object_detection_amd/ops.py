@@ -571,9 +571,12 @@ def li_heads(spk: torch.Tensor, K: int, w_heads_packed: torch.Tensor, NA: int, N
 # ---------------------------------------------------------------------------------------------
 class _Workspace:
     """grow-only scratch buffer per (device, stream) (the C ABI never allocates).  Calls on one stream reuse it in
-    stream order; calls on different streams get different buffers, so they may overlap."""
+    stream order; calls on different streams get different buffers, so they may overlap.  A buffer handed out while its stream
+    is capturing is held by a graph from then on, which writes into it on every replay: such a buffer is kept for the life of the
+    process (``captured``), whatever a later, larger call on the same stream replaces it with."""
     def __init__(self):
         self.buf = {}
+        self.captured = []
 
     def get(self, device: torch.device, nbytes: int) -> torch.Tensor:
         key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
@@ -581,6 +584,8 @@ class _Workspace:
         if b is None or b.numel() < nbytes:
             b = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
             self.buf[key] = b
+        if torch.cuda.is_current_stream_capturing() and not any(c is b for c in self.captured):
+            self.captured.append(b)
         return b
 
 
@@ -972,7 +977,9 @@ def nms_keep_mask(boxes: torch.Tensor, scores: torch.Tensor, idxs: Optional[torc
     _lib.check(lib.snn_nms_sorted(_ptr(b), _ptr(cat), n, nms_threshold_f32(iou_threshold), n, _ptr(keep), _ptr(n_keep), _ptr(ws),
                                   ws.numel(), _stream()), "snn_nms_sorted")
     kept = torch.zeros((n + 1,), dtype=torch.bool, device=boxes.device)
-    kept[keep.to(torch.int64)] = True
+    # (index_fill_ takes True as a kernel argument; ``kept[keep] = True`` copies a host scalar to the device first, which is a host-to-device
+    # copy per call and is refused while the stream is capturing)
+    kept.index_fill_(0, keep.to(torch.int64), True)
     return order, kept[:n]
 
 

@@ -75,6 +75,13 @@ class GuardedWorkspace:
         self.sizes, self.high = [], 0
         self.forget()
 
+    def rearm(self, fill: int) -> None:
+        """arm() for a region that is still in use: a captured graph holds the view handed out during its capture and no `get` runs when it is
+        replayed, so the fill and the guards are renewed while the view, its size and the largest region so far stay as they are"""
+        size, view, sizes, high = self.size, self.view, self.sizes, self.high
+        self.arm(fill)
+        self.size, self.view, self.sizes, self.high = size, view, sizes, high
+
     @staticmethod
     def _first_bad(t: torch.Tensor, byte: int) -> Optional[int]:
         bad = (t != byte).nonzero()
