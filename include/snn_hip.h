@@ -163,7 +163,7 @@ int snn_rpn_head_forward(const snn_rpn_level* levels_host, int n_levels, int C, 
  * stage-by-stage caller must run the stages in order on the SAME workspace with IDENTICAL arguments (levels, C, A, T, params,
  * weights, spike_counts null or not) and an unchanged environment; a later stage after anything else has used the workspace, or
  * with other arguments, computes on stale bytes (no error is raised: the library cannot tell).  Inspect hidden spike planes through
- * snn_debug_last_rpn_planes (snn_hip_debug.h), not by reading the workspace. */
+ * snn_rpn_head_planes_view and the spike taps (below), not by guessing at the workspace. */
 #define SNN_STAGE_ENCODE 1
 #define SNN_STAGE_CONV_LIF 2
 #define SNN_STAGE_LI_HEADS 4
@@ -609,6 +609,72 @@ int snn_encode_nchw_typed(const void* feat, int feat_dtype, int N, int C, int H,
 int snn_roi_align_encode_typed(const snn_roi_level* levels_host, int feat_dtype, int n_levels, int C, const float* rois,
                                const int* roi_batch, const int* roi_level, int R, int T, const snn_params* p_host, uint32_t* planes,
                                size_t plane_stride_words, float* pooled_dbg, snn_stream_t stream);
+
+/* ---- spike taps: rasters and activity statistics of the hidden LIF layers -------------------------------------------
+ * A head pass leaves the spike planes of its hidden LIF layers - the RPN's shared LIF, the detector's lif6 and lif7 - in the CALLER's
+ * workspace.  The two *_planes_view calls say where and in which layout; the three tap calls read planes through such a view.
+ *
+ * snn_planes_view: `steps_formed` steps of `rows` x `words` 32-bit words (bit b of word w = spike of column 32 w + b; rows = P positions in
+ * the order of the head's outputs, or R RoIs), step t at word offset t * step_stride_words behind workspace + offset_bytes, inside a step:
+ *   SNN_PLANES_ROWS        word w of row r at  r * words + w
+ *   SNN_PLANES_SPLIT4      ... at  ((w / 4) * rows + r) * 4 + w % 4     (blocks of four words; words % 4 == 0)
+ *   SNN_PLANES_WORD_MAJOR  ... at  w * rows + r
+ * These three are all the layouts a head pass writes today, for every precision and every SNN_PLANES setting; a further layout would
+ * be a further enumerator.  The view queries are HOST-ONLY (no stream, no device work, no workspace pointer): they are answered from the
+ * arguments of the pass by the plan code the forward itself runs, so a pass with these arguments and an unchanged environment (the SNN_*
+ * knobs) leaves its planes exactly there.  The arguments are those of the forward; `route` is the SNN_ROUTE_* of a *_routed entry
+ * (SNN_ROUTE_SPARSE for every other entry); spike_rates != 0: the pass is handed the spike-rate side outputs (spike_counts /
+ * spk6_count non-null).  The row-fed detector entries take word-major planes only for a 16-byte aligned x; the view assumes one.
+ * offset_bytes + T * step_stride_words * 4 never exceeds the matching snn_*_workspace_bytes[_routed] size.
+ *
+ * steps_formed = the number of leading steps whose planes the pass FORMS.  A pass computes no more than its outputs need (dead time
+ * steps: an input current first moves a spike one step later).  Without the side outputs lif6's spikes of the last step reach nothing -
+ * fc7's current of step T - 1 cannot move a lif7 spike any more - so fc6 forms the currents of steps 0 .. T - 3 only, and lif6's plane
+ * of step T - 1 is integrated without its input: steps_formed = T - 1 for T >= 3 (snn_debug_tile_shape reports the same window).  With
+ * the side outputs every spike is counted, fc6's window is one step longer and all T planes are formed.  The shared LIF and lif7 feed
+ * LI cells that read every step, in both update orders (the passes do not shorten the last step under li_order = 1), so their
+ * steps_formed is T.  A tap on steps at or past steps_formed returns -1 with nothing enqueued.
+ *
+ * There is no separate "tapped" forward: the pass to tap for statistics is the existing spike-rate-mode pass (side outputs non-null),
+ * which returns outputs, counts and time sums together.  The planes stay valid until the next call that is handed the same workspace.
+ *
+ * The taps (all three: every output nullable, enqueued on `stream`, no host synchronisation, hipGraph-capturable under the capture
+ * contract above; bad arguments - a null workspace or view, an unknown layout, T' outside 1 .. steps_formed, shapes outside the view -
+ * return -1 before any device work):
+ *   snn_planes_counts       spike counts of the steps t < T' over `n_groups` groups of rows; group g = rows group_row_start_host[g] ..
+ *                           group_row_start_host[g + 1] - 1 (host array of n_groups + 1 non-decreasing values within 0 .. rows: an image
+ *                           of a level for the RPN, an image's RoIs for the detector; n_groups <= 512, rows < 2^31).
+ *                             per_step uint64 [T'][n_groups]       spikes of step t in group g
+ *                             per_col  uint32 [n_groups][n_cols]   spikes of column c in group g, summed over its rows and the T' steps
+ *                             per_row  uint32 [rows]               spikes of row r, summed over the columns and the T' steps (rows outside
+ *                                                                  every group: 0)
+ *                           n_cols <= 32 * words (<= 8192); bits at or above n_cols - the padding of a row's last word - are never
+ *                           counted.  The counters are cleared by work of this call on the stream.
+ *   snn_planes_raster_nchw  one RPN level as bytes {0, 1}: out [T'][N][C][H][W], channel c of position (n, y, x) = bit c of row
+ *                           row0 + (n H + y) W + x (row0 = the level's first row: sum of N H W of the levels before it).
+ *   snn_planes_raster_rows  out [T'][rows][n_cols], byte (t, r, c) = bit c of row r.
+ * Encoder planes are not part of this: most plans keep them as period planes or compressed.  snn_encode_nchw / snn_encode_rows return
+ * them on request as [T][rows][words], and the raster calls read that output with a hand-filled view {0, rows * words, rows, words,
+ * SNN_PLANES_ROWS, T, 0} and the plane tensor as `workspace`. */
+enum { SNN_PLANES_ROWS = 0,        /* [T][rows][words]                       */
+       SNN_PLANES_SPLIT4 = 1,      /* [T][words/4][rows][4]                  */
+       SNN_PLANES_WORD_MAJOR = 2   /* [T][words][rows]                       */ };
+typedef struct snn_planes_view {
+    uint64_t offset_bytes;         /* into the caller's workspace            */
+    uint64_t step_stride_words;
+    int64_t  rows;                 /* P or R                                 */
+    int32_t  words, layout, steps_formed, reserved;
+} snn_planes_view;
+int snn_rpn_head_planes_view(const snn_rpn_level* levels_host, int n_levels, int C, int A, int T, const snn_params* p_host, int route,
+                             int spike_rates, snn_planes_view* shared_lif);
+int snn_det_head_planes_view(int R, int D, int Hd, int K, int K4, int T, const snn_params* p_host, int w6_inner, int route,
+                             int spike_rates, snn_planes_view* lif6, snn_planes_view* lif7 /* either may be null */);
+int snn_planes_counts(const void* workspace, const snn_planes_view* view, const int64_t* group_row_start_host, int n_groups, int n_cols,
+                      int T_prime, unsigned long long* per_step, uint32_t* per_col, uint32_t* per_row, snn_stream_t stream);
+int snn_planes_raster_nchw(const void* workspace, const snn_planes_view* view, int64_t row0, int N, int C, int H, int W, int T_prime,
+                           uint8_t* out, snn_stream_t stream);
+int snn_planes_raster_rows(const void* workspace, const snn_planes_view* view, int n_cols, int T_prime, uint8_t* out,
+                           snn_stream_t stream);
 
 #ifdef __cplusplus
 }

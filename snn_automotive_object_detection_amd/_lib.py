@@ -42,6 +42,14 @@ class snn_rpn_post_level(C.Structure):
                 ("stride_h", C.c_float), ("stride_w", C.c_float), ("base_anchors", (C.c_float * 4) * 16)]
 
 
+PLANE_LAYOUTS = {"rows": 0, "split4": 1, "word_major": 2}   # SNN_PLANES_*
+
+
+class snn_planes_view(C.Structure):
+    _fields_ = [("offset_bytes", C.c_uint64), ("step_stride_words", C.c_uint64), ("rows", C.c_int64), ("words", C.c_int32),
+                ("layout", C.c_int32), ("steps_formed", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/snn_hip_debug.h declares (test plumbing of the same .so, not the drop-in boundary)
 DEBUG_SYMBOLS = {
     "snn_debug_reload_knobs": (None, []),
@@ -195,10 +203,22 @@ SYMBOLS = {
     "snn_encode_nchw_typed": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.POINTER(snn_params), C.c_void_p, C.c_size_t, c_stream]),
     "snn_roi_align_encode_typed": (C.c_int, [C.POINTER(snn_roi_level), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
+    # spike taps (taps.py): where a head pass leaves its hidden spike planes (host-only queries), then counts and rasters read through a view
+    "snn_rpn_head_planes_view": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(snn_params), C.c_int, C.c_int,
+                                           C.POINTER(snn_planes_view)]),
+    "snn_det_head_planes_view": (C.c_int, [C.c_int] * 6 + [C.POINTER(snn_params), C.c_int, C.c_int, C.c_int, C.POINTER(snn_planes_view),
+                                                           C.POINTER(snn_planes_view)]),
+    "snn_planes_counts": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, c_stream]),
+    "snn_planes_raster_nchw": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         c_stream]),
+    "snn_planes_raster_rows": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int, C.c_int, C.c_void_p, c_stream]),
 }
 
 _LIB = None
-_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_debug_last_enc_mode")
+_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_debug_last_enc_mode",
+                # (an A/B library from before the spike taps: taps.py then raises AttributeError)
+                "snn_rpn_head_planes_view", "snn_det_head_planes_view", "snn_planes_counts", "snn_planes_raster_nchw", "snn_planes_raster_rows")
 
 
 class SnnHipError(RuntimeError):

@@ -158,6 +158,7 @@ __global__ void k_pack_heads(const float* __restrict__ wa, int NA, const float* 
 #include "snn_mx.h"
 
 #include "snn_affine.h"
+#include "snn_taps.h"
 
 // ================================================================================================
 // C ABI
@@ -2039,6 +2040,22 @@ static RpnCall rpn_call(const snn_rpn_level* lv, int fdt, int n_levels, int C, i
                    ws, ws_bytes, stream, SNN_STAGE_ALL, nullptr, 0, SPARSE_ROUTE, "snn_rpn_head_forward"};
 }
 
+// bf16x3 conv -> LI heads: spike planes in blocks of four words when the heads kernel that will run reads them so (C = 256).
+// Decided up front, so that a stage-by-stage caller (bench.py's kernel breakdown) sees the same launches; a T that does
+// not fit a row tile runs the register-fused conv, which writes plain rows: then the heads read plain rows
+static bool rpn_planes_split(const snn_params* p, int C, int A, int T) {
+    return prec_family(p) == SNN_PRECISION_BF16X3 && !knobs().spk_rows && li_heads_reads_split(C, A, 4 * A) &&
+           !knobs().bf16x3_lif_reg && cdiv(C, 32) * 32 % 128 == 0 &&
+           g3_some_tile_ok(lif_window_full_out(T).n, true);
+}
+// where an RPN pass leaves the shared LIF's spike planes (snn_rpn_head_planes_view; the pass reads its own layout from here)
+static void rpn_planes_view(const snn_params* p, long long P, int C, int A, int T, size_t o_spk, snn_planes_view* v) {
+    v->offset_bytes = o_spk; v->step_stride_words = (uint64_t)P * cdiv(C, 32); v->rows = P; v->words = cdiv(C, 32);
+    v->layout = rpn_planes_split(p, C, A, T) ? SNN_PLANES_SPLIT4 : SNN_PLANES_ROWS;
+    v->steps_formed = min(T, lif_window_full_out(T).n + 1);      // currents of steps 0 .. n - 1 form the spikes of steps 0 .. n
+    v->reserved = 0;
+}
+
 // the RPN head: encoder, conv + LIF, then the LI heads - one readout at T (the plain forward), or the readout set with its spike counts
 static int rpn_head_run(const RpnCall& c) {
     const snn_rpn_level* const lv = c.lv;
@@ -2078,12 +2095,9 @@ static int rpn_head_run(const RpnCall& c) {
     // period planes (snn_common.h): the encoder writes e_n = (first spike at step n - 1), the conv tile accumulates u_n = W e_n and
     // its LIF epilogue adds up the divisors' u_n - a quarter of the operand switching in the power-limited matrix-core loop
     const bool per = knobs().periods && periods_possible(p) && g3_some_tile_ok(Tc, true);
-    // bf16x3 conv -> LI heads: spike planes in blocks of four words when the heads kernel that will run reads them so (C = 256).
-    // Decided up front, so that a stage-by-stage caller (bench.py's kernel breakdown) sees the same launches; a T that does
-    // not fit a row tile runs the register-fused conv, which writes plain rows: then the heads read plain rows
-    bool split = prec_family(p) == SNN_PRECISION_BF16X3 && !knobs().spk_rows && li_heads_reads_split(C, A, 4 * A) &&
-                 !knobs().bf16x3_lif_reg && cdiv(C, 32) * 32 % 128 == 0 &&
-                 g3_some_tile_ok(Tc, true);
+    snn_planes_view pv;                              // the shared LIF's planes: blocks of four words or rows (rpn_planes_split)
+    rpn_planes_view(p, P, C, A, T, o_spk, &pv);
+    bool split = pv.layout == SNN_PLANES_SPLIT4;
     // bf16x3: encoder planes word-major [T][Cw][Pe] - a conv tile's spike words of a chunk are then 128-byte runs (L2 read
     // requests of the launch 1.98e8 -> 1.68e8, conv+LIF -1.1 %).  Round 2 kept the convolution on row-major planes because a
     // 128-byte line of a word plane is shared by horizontally adjacent tiles, which then sat on different XCDs (FETCH_SIZE
@@ -2176,7 +2190,8 @@ static int rpn_head_run(const RpnCall& c) {
             SNN_CHECK_LAUNCH("k_route_decide");
         }
     }
-    g_last_rpn_planes[0] = o_spk; g_last_rpn_planes[1] = split ? 1 : 0; g_last_rpn_planes[2] = (unsigned long long)P;
+    if (split != (pv.layout == SNN_PLANES_SPLIT4)) return fail(-3, "%s: the conv left another spike-plane layout than planned (internal)", c.who);
+    g_last_rpn_planes[0] = pv.offset_bytes; g_last_rpn_planes[1] = split ? 1 : 0; g_last_rpn_planes[2] = (unsigned long long)pv.rows;
     if (!(stage_mask & SNN_STAGE_LI_HEADS)) return 0;
     if (!c.steps)
         return li_heads_impl(spk, stride, T, (int)P, C, c.w_heads_packed, A, 4 * A, p, c.out_logits, c.out_bbox, c.sum_logits,
@@ -2663,6 +2678,21 @@ struct DetPlan {
     bool gated;
 };
 
+// where a detector pass with this plan leaves lif6's / lif7's spike planes (snn_det_head_planes_view; the pass reads its own layout from here).
+// Currents of steps t0 .. t0 + n - 1 (zero before t0) form the spikes of steps 0 .. t0 + n
+static void det_planes_views(const DetPlan& dp, int R, int Hd, int T, snn_planes_view* v6, snn_planes_view* v7) {
+    const int Hw = cdiv(Hd, 32);
+    for (int i = 0; i < 2; ++i) {
+        snn_planes_view* v = i ? v7 : v6;
+        if (!v) continue;
+        const StepWindow& w = i ? dp.win.fc7 : dp.win.fc6;
+        v->offset_bytes = i ? dp.o_s7 : dp.o_s6; v->step_stride_words = (uint64_t)R * Hw; v->rows = R; v->words = Hw;
+        v->layout = (!i && dp.wm) ? SNN_PLANES_WORD_MAJOR : SNN_PLANES_ROWS;          // (fc7's spikes feed the LI heads row-major)
+        v->steps_formed = min(T, w.t0 + w.n + 1);
+        v->reserved = 0;
+    }
+}
+
 // will fc6 run the structured-sparse launch on the word-major period planes at o_enc?  fc6's own launcher is asked (nothing is enqueued)
 static bool det_fc6_sparse_plan(const DetCall& c, int D, const DetPlan& dp) {
     Gemm3Args a6;
@@ -2745,7 +2775,9 @@ static int det_head_from_planes(const DetCall& c, int D, const DetPlan& dp, bool
     uint32_t* s6 = (uint32_t*)((char*)ws + o_s6);
     uint32_t* s7 = (uint32_t*)((char*)ws + o_s7);
     const int Hw = cdiv(Hd, 32), Hp = Hw * 32;
-    g_last_det_planes[0] = o_s6; g_last_det_planes[1] = o_s7; g_last_det_planes[2] = enc_wm ? 1 : 0;
+    snn_planes_view v6, v7;
+    det_planes_views(dp, R, Hd, T, &v6, &v7);
+    g_last_det_planes[0] = v6.offset_bytes; g_last_det_planes[1] = v7.offset_bytes; g_last_det_planes[2] = v6.layout == SNN_PLANES_WORD_MAJOR ? 1 : 0;
     int rc;
     if (k_inner > 1 && !folded && !dp.bin_major) {
         // fc6's weights were packed in the permuted reduction order k' = s * C + c (snn_pack_linear_weight_bf16x3_perm): bring the
@@ -3083,6 +3115,122 @@ int snn_det_exchange_payload(const float* class_logits, const float* box_regress
         hipLaunchKernelGGL(k_det_payload<4>, dim3(N), dim3(1024), (size_t)npad * 8, (hipStream_t)s, class_logits,
                            box_regression, rois_per_image, K, max_det, npad, payload, counts);
     SNN_CHECK_LAUNCH("k_det_payload");
+    return 0;
+}
+
+// ---- spike taps (kernels: snn_taps.h) ----
+static_assert(SNN_PLANES_ROWS == TAP_LAYOUT_ROWS && SNN_PLANES_SPLIT4 == TAP_LAYOUT_SPLIT4 && SNN_PLANES_WORD_MAJOR == TAP_LAYOUT_WORD_MAJOR,
+              "snn_taps.h addresses the layouts of include/snn_hip.h");
+
+// host-only: the plan code of rpn_head_run answers (rpn_ws_layout, rpn_planes_view), nothing is enqueued
+int snn_rpn_head_planes_view(const snn_rpn_level* lv, int n_levels, int C, int A, int T, const snn_params* p, int route, int spike_rates,
+                             snn_planes_view* shared_lif) {
+    (void)spike_rates;                               // (the shared LIF's planes are the same with and without the side outputs)
+    if (!lv || !p || !shared_lif) return fail(-1, "snn_rpn_head_planes_view: null argument");
+    if (n_levels <= 0 || n_levels > SNN_MAX_LEVELS || C <= 0 || A <= 0) return fail(-1, "snn_rpn_head_planes_view: bad n_levels / C / A");
+    if (!route_known(route)) return fail(-1, "snn_rpn_head_planes_view: unknown route %d", route);
+    if (prec_family(p) != SNN_PRECISION_F32 && prec_family(p) != SNN_PRECISION_BF16X3 && prec_family(p) != SNN_PRECISION_MXFP6)
+        return fail(-1, "snn_rpn_head_planes_view: unknown precision %d", p->precision);
+    if (check_T(T, "snn_rpn_head_planes_view")) return -1;
+    for (int l = 0; l < n_levels; ++l)
+        if (lv[l].N <= 0 || lv[l].H <= 0 || lv[l].W <= 0) return fail(-1, "snn_rpn_head_planes_view: bad level %d", l);
+    const long long P = rpn_positions(lv, n_levels, nullptr);
+    size_t o_spk, o_cur, o_cnt, need;
+    rpn_ws_layout(P, prec_family(p) != SNN_PRECISION_F32 ? rpn_positions_padded(lv, n_levels) : 0, C, T, prec_family(p), &o_spk, &o_cur, &o_cnt, &need);
+    rpn_planes_view(p, P, C, A, T, o_spk, shared_lif);
+    return 0;
+}
+
+// host-only: det_plan answers (the plan of det_head_run for both feeds; a row-fed x is taken as 16-byte aligned), nothing is enqueued
+int snn_det_head_planes_view(int R, int D, int Hd, int K, int K4, int T, const snn_params* p, int w6_inner, int route, int spike_rates,
+                             snn_planes_view* lif6, snn_planes_view* lif7) {
+    if (!p || (!lif6 && !lif7)) return fail(-1, "snn_det_head_planes_view: null argument");
+    if (R <= 0 || D <= 0 || Hd <= 0 || K <= 0 || K4 <= 0) return fail(-1, "snn_det_head_planes_view: bad shape");
+    if (!route_known(route)) return fail(-1, "snn_det_head_planes_view: unknown route %d", route);
+    if (prec_family(p) != SNN_PRECISION_F32 && prec_family(p) != SNN_PRECISION_BF16X3 && prec_family(p) != SNN_PRECISION_MXFP6)
+        return fail(-1, "snn_det_head_planes_view: unknown precision %d", p->precision);
+    uint32_t counted = 0;                            // (the plan asks only whether the side outputs are there)
+    DetCall c = det_call(SNN_FEAT_F32, R, Hd, K, K4, T, p, nullptr, w6_inner, nullptr, nullptr, nullptr, nullptr, spike_rates ? &counted : nullptr,
+                         spike_rates ? &counted : nullptr, nullptr, nullptr, nullptr, ~(size_t)0, nullptr);
+    feed_rows(c, nullptr, D);
+    c.who = "snn_det_head_planes_view";
+    c.route = routed(route, 0.0f, nullptr, spike_rates != 0);       // (no route_stat: nothing is gated - the gate moves no spike plane)
+    DetPlan dp;
+    const int rc = det_plan(c, D, encode_rows_wm_ok(nullptr, D), &dp);
+    if (rc) return rc;
+    det_planes_views(dp, R, Hd, T, lif6, lif7);
+    return 0;
+}
+
+// what the three taps check of their view; -> the kernels' form of it
+static int tap_view(const char* who, const void* ws, const snn_planes_view* v, int T, TapView* out) {
+    if (!ws || !v) return fail(-1, "%s: null workspace or view", who);
+    if (v->layout != SNN_PLANES_ROWS && v->layout != SNN_PLANES_SPLIT4 && v->layout != SNN_PLANES_WORD_MAJOR)
+        return fail(-1, "%s: unknown plane layout %d", who, v->layout);
+    if (v->rows <= 0 || v->rows > 0x7fffffffLL || v->words <= 0 || v->words > TAP_MAX_WORDS || (v->layout == SNN_PLANES_SPLIT4 && v->words % 4) ||
+        v->offset_bytes % 4 || v->step_stride_words < (uint64_t)v->rows * v->words)
+        return fail(-1, "%s: bad view (1 <= rows < 2^31, 1 <= words <= %d - a multiple of 4 in blocks of four -, a step stride of at least rows x words)", who, TAP_MAX_WORDS);
+    if (v->steps_formed < 1 || v->steps_formed > SNN_MAX_STEPS) return fail(-1, "%s: steps_formed = %d outside [1, %d]", who, v->steps_formed, SNN_MAX_STEPS);
+    if (T < 1 || T > v->steps_formed) return fail(-1, "%s: %d steps asked of a view whose pass forms %d", who, T, v->steps_formed);
+    out->planes = (const uint32_t*)((const char*)ws + v->offset_bytes);
+    out->step_stride = v->step_stride_words; out->rows = v->rows; out->words = v->words; out->layout = v->layout;
+    return 0;
+}
+
+int snn_planes_counts(const void* ws, const snn_planes_view* view, const int64_t* group_row_start, int n_groups, int n_cols, int T,
+                      unsigned long long* per_step, uint32_t* per_col, uint32_t* per_row, snn_stream_t stream) {
+    TapView v;
+    if (tap_view("snn_planes_counts", ws, view, T, &v)) return -1;
+    if (!group_row_start || n_groups < 1 || n_groups > TAP_MAX_GROUPS) return fail(-1, "snn_planes_counts: 1 .. %d groups", TAP_MAX_GROUPS);
+    if (n_cols < 1 || n_cols > 32 * v.words) return fail(-1, "snn_planes_counts: n_cols = %d outside 1 .. 32 x words = %d", n_cols, 32 * v.words);
+    TapGroups g;
+    g.n = n_groups;
+    long long most = 0;
+    for (int i = 0; i <= n_groups; ++i) {
+        const long long r = group_row_start[i];
+        if (r < 0 || r > v.rows || (i && r < group_row_start[i - 1]))
+            return fail(-1, "snn_planes_counts: group_row_start[%d] = %lld (non-decreasing values in 0 .. rows = %lld)", i, r, v.rows);
+        if (i) most = max(most, r - group_row_start[i - 1]);
+        g.start[i] = (int)r;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!per_step && !per_col && !per_row) return 0;
+    const size_t n_step = (size_t)T * n_groups, n_col = (size_t)n_groups * n_cols, n_row = (size_t)v.rows;
+    hipLaunchKernelGGL(k_planes_clear, dim3(min(cdiv((long long)max(n_step, max(n_col, n_row)), 256), 1024)), dim3(256), 0, s, per_step, n_step, per_col,
+                       n_col, per_row, n_row);
+    SNN_CHECK_LAUNCH("k_planes_clear");
+    if (!most) return 0;
+    hipLaunchKernelGGL(k_planes_counts, dim3(min(cdiv(most, TAP_ROWS), 1024), n_groups), dim3(256), TAP_COUNTS_LDS(v.words), s, v, g, n_cols, T,
+                       per_step, per_col, per_row);
+    SNN_CHECK_LAUNCH("k_planes_counts");
+    return 0;
+}
+
+int snn_planes_raster_nchw(const void* ws, const snn_planes_view* view, int64_t row0, int N, int C, int H, int W, int T, uint8_t* out,
+                           snn_stream_t stream) {
+    TapView v;
+    if (tap_view("snn_planes_raster_nchw", ws, view, T, &v)) return -1;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || C > 32 * v.words || (long long)H * W > 0x7fffffffLL || (long long)T * N > 65535)
+        return fail(-1, "snn_planes_raster_nchw: bad shape (C <= 32 x words = %d, T' x N <= 65535)", 32 * v.words);
+    const long long HW = (long long)H * W;
+    if (row0 < 0 || row0 + N * HW > v.rows) return fail(-1, "snn_planes_raster_nchw: rows %lld .. %lld outside the view's %lld", (long long)row0, (long long)row0 + N * HW, v.rows);
+    if (!out) return 0;
+    const int vec = HW % 16 == 0 && ((uintptr_t)out & 15) == 0;
+    hipLaunchKernelGGL(k_planes_raster_nchw, dim3(cdiv(HW, TAP_ROWS), cdiv(cdiv(C, 32), TAP_TW), T * N), dim3(256), 0, (hipStream_t)stream, v,
+                       (long long)row0, N, C, (int)HW, out, vec);
+    SNN_CHECK_LAUNCH("k_planes_raster_nchw");
+    return 0;
+}
+
+int snn_planes_raster_rows(const void* ws, const snn_planes_view* view, int n_cols, int T, uint8_t* out, snn_stream_t stream) {
+    TapView v;
+    if (tap_view("snn_planes_raster_rows", ws, view, T, &v)) return -1;
+    if (n_cols < 1 || n_cols > 32 * v.words) return fail(-1, "snn_planes_raster_rows: n_cols = %d outside 1 .. 32 x words = %d", n_cols, 32 * v.words);
+    if (!out) return 0;
+    const int vec = n_cols % 16 == 0 && ((uintptr_t)out & 15) == 0;
+    hipLaunchKernelGGL(k_planes_raster_rows, dim3(cdiv(v.rows, TAP_ROWS), cdiv(cdiv(n_cols, 32), TAP_TW), T), dim3(256), 0, (hipStream_t)stream, v,
+                       n_cols, out, vec);
+    SNN_CHECK_LAUNCH("k_planes_raster_rows");
     return 0;
 }
 

@@ -38,6 +38,25 @@ def extract_spike_rates(model, batches: Iterable[List[torch.Tensor]]) -> Dict[in
     return {k: torch.cat(v, dim=0) for k, v in per_layer.items()}
 
 
+@torch.no_grad()
+def rates_from_taps(taps, to_cpu: bool = True) -> Dict[int, torch.Tensor]:
+    """The rate rows of spike-rate mode from tapped passes (GeneralizedRCNN.forward_tapped): ``taps`` is one ``{"rpn": ..., "det": ...}``
+    dict or a sequence of them, one per batch.  The counts and time sums each pass returned go through the same snn_rpn_rates /
+    snn_det_rates that spike-rate mode runs, so the result is bit-equal to ``extract_spike_rates`` on the same batches - per list
+    position the concatenation over the batches, on the CPU - and ``energy_report`` takes it unchanged: one detection pass yields the
+    detections and the energy figure.  A head-level taps dict (RPNHeadSNN / FastRCNNPredictorSNNFull.forward_tapped) gives that head's
+    positions alone, counted from 0."""
+    from . import taps as _taps
+    per_layer = defaultdict(list)
+    for t in ([taps] if isinstance(taps, dict) else taps):
+        rows = []
+        for part in ([t["rpn"], t["det"]] if "rpn" in t else [t]):
+            rows += _taps.rpn_rate_list(part) if "shared_lif" in part else _taps.det_rate_list(part)
+        for i, r in enumerate(rows):
+            per_layer[i].append(r.detach().cpu() if to_cpu else r.detach())
+    return {k: torch.cat(v, dim=0) for k, v in per_layer.items()}
+
+
 def energy_report(rates: Dict[int, torch.Tensor], timesteps_rpn: int, timesteps_detector: int) -> Dict:
     """train.py:470-515 as data: per layer the mean number of spikes over the T steps, the FLOPs figure, the ANN
     and SNN energies in joule and their ratio; plus the totals."""

@@ -158,6 +158,31 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
                                                      **self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1]))
         return self._finish_readouts(out, steps)
 
+    @torch.no_grad()
+    def forward_tapped(self, x, raster: bool = False, rois_per_image=None):
+        """``(class_logits, box_regression, taps)``: the head's outputs together with the spike taps of lif6 and lif7, from ONE pass.
+        ``taps["lif6"]`` / ``taps["lif7"]``: ``per_step`` [n_images, T] int64, ``per_channel`` [n_images, representation_size] and
+        ``per_roi`` [R] (int32, summed over the T steps) and, with ``raster``, ``raster`` [T, R, representation_size] torch.bool.
+        ``rois_per_image``: how many consecutive RoIs belong to each image (None: one image).  ``taps["pass"]``: the pass's own per-RoI
+        counts and time sums (energy.rates_from_taps).
+        The pass is the one spike-rate mode runs, bit for bit (outputs, counts, sums) - the plan of spike-rate mode, whose fc6 window is
+        one step longer so that every lif6 plane is formed, not a promise about the launches of a plain ``forward``.  ``spike_rates``,
+        ``num_steps`` and ``route_stat`` are not touched (spike-rate mode runs the plain fc6 plan on every route)."""
+        from . import taps as _taps
+        x = x.flatten(start_dim=1)
+        args = self._pass_args(x.shape[1], "%d" % x.shape[1])
+        return _taps.det_head_tapped(x, T=int(self.num_steps), raster=raster, rois_per_image=rois_per_image, only_one_bbox=self.only_one_bbox, **args)
+
+    @torch.no_grad()
+    def forward_roialign_tapped(self, feats, scales, rois, roi_level, roi_batch=None, raster: bool = False, rois_per_image=None):
+        """``forward_tapped`` for the head fed straight from the FPN maps (see ``forward_roialign`` for the RoI arguments)"""
+        from . import taps as _taps
+        if roi_batch is None:
+            rois, roi_batch = rois[:, 1:5], rois[:, 0]
+        args = self._pass_args(feats[0].shape[1] * 49, "%d x 49" % feats[0].shape[1])
+        return _taps.det_head_roialign_tapped(feats, scales, rois, roi_batch, roi_level, T=int(self.num_steps), raster=raster,
+                                              rois_per_image=rois_per_image, only_one_bbox=self.only_one_bbox, **args)
+
     def _rates(self, extras, T):
         """faster_rcnn.py:568-618: four [R, 2] = (rate, "FLOPs") tensors - lif6, lif7, cls_score, bbox_pred - finished by
         snn_det_rates from the integer spike counts of the LIF epilogues and the time-summed LI membranes (one launch)"""

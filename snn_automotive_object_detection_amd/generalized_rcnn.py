@@ -58,6 +58,26 @@ class GeneralizedRCNN(nn.Module):
         out["proposals"] = out["proposals"] * scale
         return out
 
+    @torch.no_grad()
+    def forward_tapped(self, images: List[Tensor], raster: bool = False):
+        """``(detections, taps)``: what ``forward`` returns, and ``taps = {"rpn": ..., "det": ...}`` - the spike taps of the hidden LIF
+        layers of both heads (RPNHeadSNN.forward_tapped, RoIHeadsSNN.forward_tapped) - from the SAME two head passes.  The passes are
+        those of spike-rate mode, so ``energy.rates_from_taps(taps)`` gives its rate rows as well: one detection pass yields detections
+        and the energy report.  The heads' ``spike_rates`` attributes are not touched."""
+        if self.training:
+            raise NotImplementedError("inference only (call .eval()): training is out of scope (DESIGN.md §7)")
+        original_image_sizes = [(int(img.shape[-2]), int(img.shape[-1])) for img in images]
+        images, _ = self.transform(images, None)
+        features = self.backbone(images.tensors)
+        if isinstance(features, torch.Tensor):
+            features = OrderedDict([("0", features)])
+        feats = list(features.values())
+        logits, bbox_reg, rpn_taps = self.rpn.head.forward_tapped(feats, raster=raster)
+        proposals, proposal_extras = self.rpn.proposals_from_head(images, feats, (logits, bbox_reg))
+        detections, det_taps = self.roi_heads.forward_tapped(features, proposals, images.image_sizes, raster=raster)
+        detections = self.finish_detections(detections, proposal_extras, images.image_sizes, original_image_sizes)
+        return detections, {"rpn": rpn_taps, "det": det_taps}
+
     def _resize_ratios(self, image_sizes, original_image_sizes, device) -> Tensor:
         """resize_boxes' ratios (fp32 new / old, as it forms them) of every image as one device tensor; uploaded once per set of sizes"""
         cache = self.__dict__.setdefault("_ratio_cache", {})

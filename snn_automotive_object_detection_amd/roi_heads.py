@@ -180,6 +180,25 @@ class RoIHeadsSNN(nn.Module):
                 "rois": rois.view(N, cap, 4), "roi_counts": counts.clamp(0, cap),
                 "class_logits": class_logits, "box_regression": box_regression}
 
+    @torch.no_grad()
+    def forward_tapped(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]], raster: bool = False):
+        """``(detections, taps)``: the list of per-image dicts ``forward`` returns, and the spike taps of lif6 and lif7 (see
+        FastRCNNPredictorSNNFull.forward_tapped; the groups of ``per_step`` / ``per_channel`` are the images), both from ONE head pass -
+        the pass of spike-rate mode, whatever the head's ``spike_rates`` says."""
+        if self.training:
+            raise NotImplementedError("inference only: training the RoI heads is out of scope (DESIGN.md §7)")
+        pool, head = self.box_roi_pool, self.box_head_and_predictor
+        per_image = [p.shape[0] for p in proposals]
+        if self._fuses_roi_align("forward_roialign_tapped"):
+            feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
+            class_logits, box_regression, taps = head.forward_roialign_tapped(feats, scales, rois, lvl, raster=raster, rois_per_image=per_image)
+        else:
+            class_logits, box_regression, taps = head.forward_tapped(pool(features, proposals, image_shapes), raster=raster, rois_per_image=per_image)
+        boxes, scores, labels, all_scores, all_boxes = self.postprocess_detections(class_logits, box_regression, proposals, image_shapes)
+        result = [{"boxes": boxes[i], "labels": labels[i], "scores": scores[i], "all_scores": all_scores[i],
+                   "all_boxes": all_boxes[i]} for i in range(len(boxes))]
+        return result, taps
+
     def head_readouts(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]], steps) -> dict:
         """the head call of ``forward`` with a readout per T_det of ``steps`` (one pass at steps[-1]; the fused RoIAlign path where
         ``forward`` takes it): {T_det: head output}"""

@@ -193,12 +193,13 @@ class RPNHeadSNN(_SpikingHead):
             w_heads = self._cache_heads.get((self.conv_cls.weight, self.conv_bbox.weight), _pack_heads_unchecked)
         return self.in_channels, self.num_anchors, self._params(prec), w_shared, w_heads
 
-    def _level_views(self, x, out_l, out_b, rows, rate_rows):
+    def _level_views(self, x, out_l, out_b, rows, rate_rows, with_rates=None):
         """what ``forward`` returns, per level, from the position-major outputs of one readout: physically NHWC; the NCHW view
         is what the reference returns (rpn.py:118-119) and makes concat_box_prediction_layers' view/permute/reshape
         (rpn.py:256-258) copy-free.  Spike rates (rpn.py:171-195): three [N, 2] = (rate, FLOPs) tensors per level, finished
         by snn_rpn_rates (views, no torch math)"""
         A = self.num_anchors
+        with_rates = self.spike_rates if with_rates is None else with_rates
         logits, bbox_reg, rates = [], [], []
         pos = 0
         for l, f in enumerate(x):
@@ -206,10 +207,10 @@ class RPNHeadSNN(_SpikingHead):
             n = rows[l]
             logits.append(out_l[pos:pos + n].view(N, H, W, A).permute(0, 3, 1, 2))
             bbox_reg.append(out_b[pos:pos + n].view(N, H, W, 4 * A).permute(0, 3, 1, 2))
-            if self.spike_rates:
+            if with_rates:
                 rates += [rate_rows[l, j, :N] for j in range(3)]
             pos += n
-        return (logits, bbox_reg, rates) if self.spike_rates else (logits, bbox_reg)
+        return (logits, bbox_reg, rates) if with_rates else (logits, bbox_reg)
 
     @torch.no_grad()
     def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
@@ -239,6 +240,22 @@ class RPNHeadSNN(_SpikingHead):
             list(x), C, A, steps, p, w_shared, w_heads, spike_rates=self.spike_rates)
         return {T: self._level_views(x, out_l[j], out_b[j], rows, rate_rows[j] if self.spike_rates else None)
                 for j, T in enumerate(steps)}
+
+    @torch.no_grad()
+    def forward_tapped(self, x: List[Tensor], raster: bool = False, levels=None):
+        """``(logits, bbox_reg, taps)``: the head's outputs together with the spike taps of its shared LIF, from ONE pass.
+        ``taps["shared_lif"]`` is a per-level list of dicts: ``per_step`` [N, T] int64 (spikes of image n at step t), ``per_channel``
+        [N, C] and ``per_position`` [N, H, W] (int32, summed over the T steps) and, with ``raster``, for the levels listed in
+        ``levels`` (None: every level - level 0 at Cityscapes size is 302 MB), ``raster`` [T, N, C, H, W] torch.bool: the spike train
+        itself.  ``taps["pass"]`` holds the pass's own spike counts and time sums (energy.rates_from_taps).
+        The pass is the one spike-rate mode runs, bit for bit (outputs, counts, sums) - the plan of spike-rate mode, which forms every
+        spike plane, not a promise about the launches of a plain ``forward``.  ``spike_rates``, ``num_steps`` and ``route_stat`` are
+        not touched (spike-rate mode runs the plain conv plan on every route)."""
+        from . import taps as _taps
+        C, A, p, w_shared, w_heads = self._pass_args()
+        out_l, out_b, rows, taps = _taps.rpn_head_tapped(list(x), C, A, int(self.num_steps), p, w_shared, w_heads, raster=raster, levels=levels)
+        logits, bbox_reg = self._level_views(x, out_l, out_b, rows, None, with_rates=False)
+        return logits, bbox_reg, taps
 
 
 # ---------------------------------------------------------------------------------------------
