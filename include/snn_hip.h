@@ -339,7 +339,8 @@ int snn_det_postprocess(const float* class_logits, const float* box_regression, 
  * snn_rpn_proposals already leaves [N][post_nms_top_n][4] padded rows and out_counts[N] in device memory.  The two calls below take
  * that layout on: every per-image row count is READ ON THE DEVICE and clamped to 0 .. cap there (a garbage count never indexes out
  * of bounds), shapes depend on (N, cap) alone, nothing waits for the host: the sequence snn_rpn_head_forward, snn_rpn_proposals,
- * snn_roi_assign, snn_det_head_forward_roialign, snn_det_postprocess_padded runs from the FPN features to the detections on one stream.
+ * snn_roi_assign, snn_det_head_forward_roialign, snn_det_postprocess_padded runs from the FPN features to the detections on one stream,
+ * and snn_pack_padded_detections (below, behind snn_det_exchange_payload) turns them into fixed-size exchange rows as a sixth call.
  * Bad arguments return -1 (limits: -4) before any device work.
  *
  * snn_roi_assign: the RoI table of snn_det_head_forward_roialign from padded proposals, one launch.  Row r = i * cap + j:
@@ -373,6 +374,20 @@ int snn_det_postprocess_padded(const float* class_logits, const float* box_regre
 int snn_det_exchange_payload(const float* class_logits /* [N*rois_per_image][K] */,
                              const float* box_regression /* [N*rois_per_image][4K] */, int N, int rois_per_image, int K,
                              int max_det, float* payload /* [N][max_det][6] */, int* counts /* [N] */, snn_stream_t stream);
+
+/* ---- padded detections -> exchange rows: the sixth call of the static-shape path --------------------------------
+ * out_* of snn_det_postprocess_padded -> the rows of dp.pack_detections, payload [N][max_det][6] fp32 (x1, y1, x2, y2, score, label) and counts [N]:
+ * the one fixed-size record a deployment copies to pinned memory or hands to the all-gather, formed without the host reading a count.
+ *   k_i = min(clamp(out_counts[i][0] + out_counts[i][1], 0, out_cap), max_det)        (on the device; the sum in 64 bits)
+ *   payload[i][r] = (out_boxes[i][r], out_scores[i][r], (float)out_labels[i][r]) for r < k_i, six zeros for r >= k_i;  counts[i] = k_i.
+ * Input rows at or past k_i are never read; every element of payload and counts is written on every call, so the outputs depend on the
+ * inputs alone.  One launch, no workspace, stream-only, capturable.  out_boxes 16-byte aligned, payload 8-byte aligned (16-byte stores
+ * when max_det is even and payload is 16-byte aligned).  Bad arguments (N < 1 or > 64, out_cap < 1, max_det < 1, a null or misaligned
+ * pointer) return -1 before any device work; max_det > 2^24 (counts travel as fp32) returns -4. */
+int snn_pack_padded_detections(const float* out_boxes /* [N][out_cap][4] */, const float* out_scores /* [N][out_cap] */,
+                               const int32_t* out_labels /* [N][out_cap] */, const int32_t* out_counts /* [N][2], device */, int N,
+                               int out_cap, int max_det, float* payload /* [N][max_det][6] */, int32_t* counts /* [N] */,
+                               snn_stream_t stream);
 
 /* ---- helper outside the spiking path: FrozenBatchNorm2d (+ residual) (+ ReLU) of the stock backbone in one pass -----
  * y[n][c][i] = relu?( (x[n][c][i] * scale[c] + bias[c]) (+ residual[n][c][i]) ), the operations of torchvision's

@@ -115,6 +115,8 @@ SYMBOLS = {
     "snn_det_postprocess_padded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "snn_pack_padded_detections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             c_stream]),
     "snn_det_exchange_payload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                            c_stream]),
     "snn_nms_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -216,7 +218,7 @@ SYMBOLS = {
 }
 
 _LIB = None
-_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_debug_last_enc_mode",
+_STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_pack_padded_detections", "snn_debug_last_enc_mode",
                 # (an A/B library from before the spike taps: taps.py then raises AttributeError)
                 "snn_rpn_head_planes_view", "snn_det_head_planes_view", "snn_planes_counts", "snn_planes_raster_nchw", "snn_planes_raster_rows")
 

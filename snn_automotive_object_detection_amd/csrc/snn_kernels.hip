@@ -2406,8 +2406,9 @@ int snn_rpn_proposals(const snn_rpn_post_level* lv, int n_levels, int N, int A, 
         // (behind the histograms: per-list count / largest coordinate of the candidates that pass the filters, for the NMS)
         a.list_cnt = (int*)(g_hist + (size_t)N * SNN_MAX_LEVELS * 2048);
         a.list_max = (uint32_t*)(a.list_cnt + (size_t)N * SNN_MAX_LEVELS);
-        if (hipMemsetAsync(g_hist, 0, ((size_t)N * SNN_MAX_LEVELS * 2048 + 2 * (size_t)N * SNN_MAX_LEVELS) * 4, s) != hipSuccess)
-            return fail(-3, "hipMemsetAsync failed");
+        const size_t n_clear = (size_t)N * SNN_MAX_LEVELS * 2048 + 2 * (size_t)N * SNN_MAX_LEVELS;     // (inside region 10: rpn_post_layout)
+        hipLaunchKernelGGL(k_topk_clear, dim3(min(cdiv((long long)n_clear, 256), 1024)), dim3(256), 0, s, g_hist, n_clear);
+        SNN_CHECK_LAUNCH("k_topk_clear");
         for (int pass = 0; pass < 3; ++pass) {
             hipLaunchKernelGGL(k_topk_hist, dim3(TOPK_CH, n_levels, N), dim3(256), 0, s, a, pass, st, g_hist, g_hist3);
             SNN_CHECK_LAUNCH("k_topk_hist");
@@ -2589,7 +2590,29 @@ int snn_roi_assign(const float* boxes, const int* counts_dev, int N, int cap, in
     return 0;
 }
 
-#define DET_SYNC_BYTES 16384                      // (a guard gap between the spike planes and the raw encoder planes; round 4 kept tile counters here)
+// ---- padded detections -> the exchange rows of the data-parallel path ------------------------------
+#define PACK_MAX_DET (1 << 24)                    // counts ride the all-gather as fp32 (dp.all_gather_detection_tensors): exact below 2^24
+int snn_pack_padded_detections(const float* out_boxes, const float* out_scores, const int32_t* out_labels, const int32_t* out_counts,
+                               int N, int out_cap, int max_det, float* payload, int32_t* counts, snn_stream_t stream) {
+    if (!out_boxes || !out_scores || !out_labels || !out_counts || !payload || !counts)
+        return fail(-1, "snn_pack_padded_detections: null argument");
+    if (N <= 0 || N > RPN_MAX_IMAGES || out_cap <= 0 || max_det <= 0)
+        return fail(-1, "snn_pack_padded_detections: bad argument (1 <= images <= %d, out_cap >= 1, max_det >= 1)", RPN_MAX_IMAGES);
+    if (((uintptr_t)out_boxes & 15) || ((uintptr_t)payload & 7))
+        return fail(-1, "snn_pack_padded_detections: out_boxes must be 16-byte aligned and payload 8-byte aligned");
+    if (max_det > PACK_MAX_DET) return fail(-4, "snn_pack_padded_detections: max_det = %d (max %d)", max_det, PACK_MAX_DET);
+    const dim3 grid(min(cdiv(max_det, PACK_ROWS), 64), N);
+    if (max_det % 2 == 0 && ((uintptr_t)payload & 15) == 0)    // every image's stripe of 24 * max_det bytes starts on a 16-byte boundary
+        hipLaunchKernelGGL(k_pack_padded_detections<4>, grid, dim3(PACK_ROWS), 0, (hipStream_t)stream, out_boxes, out_scores, out_labels,
+                           out_counts, out_cap, max_det, payload, counts);
+    else
+        hipLaunchKernelGGL(k_pack_padded_detections<2>, grid, dim3(PACK_ROWS), 0, (hipStream_t)stream, out_boxes, out_scores, out_labels,
+                           out_counts, out_cap, max_det, payload, counts);
+    SNN_CHECK_LAUNCH("k_pack_padded_detections");
+    return 0;
+}
+
+#define DET_SYNC_BYTES 16384                    // (a guard gap between the spike planes and the raw encoder planes; round 4 kept tile counters here)
 static void det_ws_layout(int R, int D, int Hd, int T, size_t* o_enc, size_t* o_cur, size_t* o_s6, size_t* o_s7,
                           size_t* total) {
     const size_t enc = align_up((size_t)T * R * cdiv(D, 32) * 4, 256);

@@ -349,6 +349,13 @@ __device__ __forceinline__ uint32_t f2key(float f) {           // monotone: larg
 #define TOPK_CH 32
 struct TopkState { uint32_t prefix, need, cnt_gt, pad; };
 
+// the list histograms and the per-list counters behind them -> zero, in front of the first histogram pass.  A launch of its own and not a
+// memset: the call is a node sequence of captured graphs (static.CapturedHeads), and memset nodes next to kernels have gone wrong under
+// replay on this runtime where the same calls were right eagerly (k_planes_clear) - the same work eagerly and in a replay
+__global__ __launch_bounds__(256) void k_topk_clear(uint32_t* __restrict__ words, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) words[i] = 0u;
+}
+
 __global__ __launch_bounds__(256) void k_topk_hist(const RpnPostArgs a, int pass, const TopkState* __restrict__ state,
                                                    uint32_t* __restrict__ g_hist, uint32_t* __restrict__ g_hist3) {
     const RpnPostLevel& L = a.lv[blockIdx.y];
@@ -844,6 +851,48 @@ __global__ __launch_bounds__(256) void k_roi_assign(const float* __restrict__ bo
     reinterpret_cast<float4*>(rois)[row] = b;
     roi_batch[row] = img;
     roi_level[row] = lvl;
+}
+
+// ------------------------------------------------------------------------------------------------
+// padded detections (out_* of snn_det_postprocess_padded) -> the exchange rows of the data-parallel path, payload [N][max_det][6] =
+// (x1, y1, x2, y2, score, label) and counts [N], one launch.  Image blockIdx.y; its blocks take tiles of PACK_ROWS output rows in turn.
+// k = min(clamp(fg + bg, 0, out_cap), max_det) is formed on the device (the sum in 64 bits: two garbage counts cannot wrap into range), so no
+// input row at or past k is read and no index leaves [0, out_cap).  A tile is gathered into LDS - one float4 of boxes, a score and a label per
+// lane, 16 + 4 + 4 coalesced bytes - and leaves as ONE contiguous run of 6 * rows floats, VEC floats per lane and store: 16 bytes when every
+// image's stripe starts on a 16-byte boundary (max_det even), else 8 (a row is 24 bytes, so 8 always divides).  Rows at or past k are
+// written as zeros: every element of payload and counts is written on every call.
+// ------------------------------------------------------------------------------------------------
+#define PACK_ROWS 256
+template <int VEC>
+__global__ __launch_bounds__(PACK_ROWS) void k_pack_padded_detections(const float* __restrict__ out_boxes, const float* __restrict__ out_scores,
+                                                                      const int* __restrict__ out_labels, const int* __restrict__ out_counts,
+                                                                      int out_cap, int max_det, float* __restrict__ payload,
+                                                                      int* __restrict__ counts) {
+    typedef float vec_t __attribute__((ext_vector_type(VEC)));
+    __shared__ __attribute__((aligned(16))) float rows[PACK_ROWS * 6];
+    const int img = blockIdx.y, tid = threadIdx.x;
+    const long long have = (long long)out_counts[2 * img] + (long long)out_counts[2 * img + 1];
+    const int k = min((int)min(max(have, 0ll), (long long)out_cap), max_det);
+    if (blockIdx.x == 0 && tid == 0) counts[img] = k;
+    const int tiles = (max_det + PACK_ROWS - 1) / PACK_ROWS;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int r0 = tile * PACK_ROWS, r = r0 + tid;
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        float sc = 0.0f, lb = 0.0f;
+        if (r < k) {                                            // (k <= out_cap: the row exists)
+            const size_t src = (size_t)img * out_cap + r;
+            b = reinterpret_cast<const float4*>(out_boxes)[src];
+            sc = out_scores[src];
+            lb = (float)out_labels[src];
+        }
+        float* mine = rows + tid * 6;
+        mine[0] = b.x; mine[1] = b.y; mine[2] = b.z; mine[3] = b.w; mine[4] = sc; mine[5] = lb;
+        __syncthreads();
+        const int n = min(PACK_ROWS, max_det - r0) * 6;         // floats of this tile; a multiple of VEC (VEC = 4: max_det and PACK_ROWS are even)
+        vec_t* dst = reinterpret_cast<vec_t*>(payload + ((size_t)img * max_det + r0) * 6);
+        for (int v = tid; v * VEC < n; v += PACK_ROWS) dst[v] = reinterpret_cast<const vec_t*>(rows)[v];
+        __syncthreads();
+    }
 }
 
 // impulse responses of the LI cell (norse leaky_integrator.py: li_feed_forward_step; v_leak = 0)

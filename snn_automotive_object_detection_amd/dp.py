@@ -224,26 +224,57 @@ def all_gather_detections(dets: List[Dict[str, torch.Tensor]], max_det: int = 11
     packed = pack_detections(dets, max_det, device, extras)
     payload, counts = packed[0], packed[1]
     extra = packed[2] if extras is not None else None
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        if images_per_rank is not None:
-            if images_per_rank < len(dets):
-                raise ValueError("images_per_rank = %d but this rank holds %d images" % (images_per_rank, len(dets)))
-            n_max = int(images_per_rank)
-        else:
-            n_max = torch.tensor([len(dets)], dtype=torch.int64, device=device if dist.get_backend() != "gloo" else "cpu")
-            dist.all_reduce(n_max, op=dist.ReduceOp.MAX)
-            n_max = int(n_max.item())
-        if n_max > len(dets):                              # short rank: pad with rows marked count = -1
-            pad = n_max - len(dets)
-            payload = torch.cat([payload, payload.new_zeros((pad, max_det, 6))], 0)
-            counts = torch.cat([counts, counts.new_full((pad,), -1)], 0)
-            if extra is not None:
-                extra = torch.cat([extra, extra.new_zeros((pad, extra.shape[1]))], 0)
+    payload, counts, extra = _pad_short_rank(payload, counts, extra, images_per_rank)
     if extra is None:
         g_payload, g_counts = all_gather_detection_tensors(payload, counts)
         return unpack_detections(g_payload, g_counts)
     g_payload, g_counts, g_extra = all_gather_detection_tensors(payload, counts, extra=extra)
     return unpack_detections(g_payload, g_counts, g_extra, extras)
+
+
+def _pad_short_rank(payload: torch.Tensor, counts: torch.Tensor, extra: Optional[torch.Tensor], images_per_rank: Optional[int]):
+    """in a group of several ranks: this rank's block padded to the largest image count of any rank (``images_per_rank``, else agreed with
+    one MAX all-reduce) with rows marked count = -1; otherwise the tensors as they came"""
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return payload, counts, extra
+    n, max_det = int(payload.shape[0]), int(payload.shape[1])
+    if images_per_rank is not None:
+        if images_per_rank < n:
+            raise ValueError("images_per_rank = %d but this rank holds %d images" % (images_per_rank, n))
+        n_max = int(images_per_rank)
+    else:
+        n_max = torch.tensor([n], dtype=torch.int64, device=payload.device if dist.get_backend() != "gloo" else "cpu")
+        dist.all_reduce(n_max, op=dist.ReduceOp.MAX)
+        n_max = int(n_max.item())
+    if n_max > n:                                          # short rank: pad with rows marked count = -1
+        pad = n_max - n
+        payload = torch.cat([payload, payload.new_zeros((pad, max_det, 6))], 0)
+        counts = torch.cat([counts, counts.new_full((pad,), -1)], 0)
+        if extra is not None:
+            extra = torch.cat([extra, extra.new_zeros((pad, extra.shape[1]))], 0)
+    return payload, counts, extra
+
+
+def all_gather_padded(out_or_rows, max_det: int = 1100, images_per_rank: Optional[int] = None) -> List[Dict[str, torch.Tensor]]:
+    """``all_gather_detections(static.unpad(out), max_det)`` without ``unpad``: the rows come from ONE kernel that reads the counts on the
+    device (ops.pack_padded_detections), so this thread does not wait for the device before the collective.  ``out_or_rows``: the dict of
+    padded detections (static.heads_padded, forward_padded, a CapturedHeads call - whose ``payload`` / ``payload_counts`` are taken as
+    they are when they have ``max_det`` rows), or the pair (payload [n, max_det, 6], counts [n]) itself.  Every rank returns the detections
+    (boxes / scores / labels) of ALL images in global image order; the host synchronisations are the collective's own and
+    ``unpack_detections``' read of the gathered counts, as in ``all_gather_detections``.  ``images_per_rank``: as there."""
+    if isinstance(out_or_rows, dict):
+        rows = (out_or_rows.get("payload"), out_or_rows.get("payload_counts"))
+        if rows[0] is None or rows[1] is None or rows[0].shape[1] != max_det:
+            from . import ops
+            rows = ops.pack_padded_detections(out_or_rows, max_det)
+    else:
+        rows = tuple(out_or_rows)
+    payload, counts = rows
+    if payload.dim() != 3 or payload.shape[1] != max_det or payload.shape[2] != 6 or tuple(counts.shape) != (payload.shape[0],):
+        raise ValueError("all_gather_padded: payload [n, %d, 6] and counts [n] expected, got %s and %s" % (max_det, tuple(payload.shape), tuple(counts.shape)))
+    payload, counts, _ = _pad_short_rank(payload, counts, None, images_per_rank)
+    g_payload, g_counts = all_gather_detection_tensors(payload, counts)
+    return unpack_detections(g_payload, g_counts)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1142,6 +1142,14 @@ def det_postprocess_padded(class_logits: torch.Tensor, box_regression: torch.Ten
     return boxes, scores, labels, out_counts, all_scores, all_boxes
 
 
+def pack_padded_detections(out, max_det: int):
+    """the sixth call of the static path: the dict of padded detections -> (payload [N, max_det, 6], counts [N] int32), the exchange rows of
+    dp.py, one launch, no host synchronisation (snn_pack_padded_detections).  The call takes the path's dict, not tensors, so it is kept with
+    the path: static.pack_padded_detections, which this name forwards to (as taps.py holds the calls of the spike taps)."""
+    from . import static
+    return static.pack_padded_detections(out, max_det)
+
+
 # ---------------------------------------------------------------------------------------------
 # device guard: every wrapper above launches on "the current stream of the current device"; a caller holding tensors on
 # another GPU of the process (cuda:1 while cuda:0 is current) gets that device made current for the call, as torch's
