@@ -691,6 +691,34 @@ int snn_planes_raster_nchw(const void* workspace, const snn_planes_view* view, i
 int snn_planes_raster_rows(const void* workspace, const snn_planes_view* view, int n_cols, int T_prime, uint8_t* out,
                            snn_stream_t stream);
 
+/* ---- readout weight gradients: exact gradients of the two LI heads' weights from a pass's spike planes ----------------
+ * The LI cell is linear and so is the bias-free 1x1 conv / linear in front of it, and the hidden spike train does not depend on the readout
+ * weights.  With out = W S, S[r][k] = sum_{t < T'} kappa_t bit_t(r, k) and kappa = the impulse responses the forward folds the LI cell into
+ * (li_kappa at T', in either li_order), the gradient of any loss with respect to the readout weights is
+ *     gw_x[j][k] (+)= sum_r grad_x[r][j] * S[r][k]              x = a (cls_logits / cls_score), b (bbox_pred)
+ * exactly: no surrogate gradient, no threshold, nothing that can flip.  Nothing else of training is here (hidden-layer gradients, losses).
+ *   - `planes` / `view`: read exactly as the spike taps read them (the workspace of the pass, or a copy of its plane region with offset_bytes
+ *     = 0); all three layouts are addressed inside the kernel; bits at or above n_cols are never read as spikes.  n_cols <= 32 * words
+ *     (<= 8192), rows < 2^31;
+ *   - T_prime in 1 .. view->steps_formed: T' = T is the gradient of the plain forward, T' < T that of the any-time readout at T';
+ *   - grad_a [rows][NA], grad_b [rows][NB] fp32, rows in the order of the head's outputs; either (grad, gw) pair may be null with its count
+ *     0; 1 <= NA + NB <= 480;
+ *   - accumulate = 0 writes every element of gw_a [NA][n_cols] / gw_b [NB][n_cols] by work of this call (nothing is cleared in front: no
+ *     memset node), accumulate = 1 adds to what they hold;
+ *   - DETERMINISTIC: no floating-point atomics.  Slabs of rows write partial sums to `scratch` (snn_li_heads_wgrad_workspace_bytes: at
+ *     most 512 x (NA + NB) x n_cols floats; monotone in every argument; 0 for a shape outside the limits), a second launch adds them in a
+ *     fixed order: two calls on the same data are bit-equal, whatever the scratch held before.  The scratch must not overlap the planes;
+ *   - rounding: S is summed in fp32 for t ascending, the products are fused multiply-adds over the rows; against exact arithmetic every
+ *     element is within (rows + 2 T' + 4) 2^-24 sum_r |grad| S;
+ *   - stream-only, no host synchronisation, hipGraph-capturable under the capture contract above; bad arguments (a null view / planes /
+ *     parameters, an unknown layout, T' outside 1 .. steps_formed, n_cols > 32 * words, NA + NB = 0 or > 480, a null pointer of a head with
+ *     outputs, a short or null scratch) return -1 with snn_last_error before any device work.  Two launches. */
+size_t snn_li_heads_wgrad_workspace_bytes(int64_t rows, int n_cols, int NA, int NB);
+int snn_li_heads_wgrad(const void* planes, const snn_planes_view* view, int n_cols, int T_prime, const snn_params* p_host,
+                       const float* grad_a /* [rows][NA] */, const float* grad_b /* [rows][NB] */, int NA, int NB,
+                       float* gw_a /* [NA][n_cols] */, float* gw_b /* [NB][n_cols] */, int accumulate, void* scratch,
+                       size_t scratch_bytes, snn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,12 +215,18 @@ SYMBOLS = {
     "snn_planes_raster_nchw": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          c_stream]),
     "snn_planes_raster_rows": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int, C.c_int, C.c_void_p, c_stream]),
+    # readout weight gradients (readout.py): planes + view, n_cols, T', params, grad_a, grad_b, NA, NB, gw_a, gw_b, accumulate, scratch, its bytes
+    "snn_li_heads_wgrad_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "snn_li_heads_wgrad": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
 }
 
 _LIB = None
 _STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_pack_padded_detections", "snn_debug_last_enc_mode",
                 # (an A/B library from before the spike taps: taps.py then raises AttributeError)
-                "snn_rpn_head_planes_view", "snn_det_head_planes_view", "snn_planes_counts", "snn_planes_raster_nchw", "snn_planes_raster_rows")
+                "snn_rpn_head_planes_view", "snn_det_head_planes_view", "snn_planes_counts", "snn_planes_raster_nchw", "snn_planes_raster_rows",
+                # (... from before the readout gradients: readout.py then raises AttributeError)
+                "snn_li_heads_wgrad_workspace_bytes", "snn_li_heads_wgrad")
 
 
 class SnnHipError(RuntimeError):

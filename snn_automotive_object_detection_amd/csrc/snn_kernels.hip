@@ -159,6 +159,7 @@ __global__ void k_pack_heads(const float* __restrict__ wa, int NA, const float* 
 
 #include "snn_affine.h"
 #include "snn_taps.h"
+#include "snn_wgrad.h"
 
 // ================================================================================================
 // C ABI
@@ -3254,6 +3255,46 @@ int snn_planes_raster_rows(const void* ws, const snn_planes_view* view, int n_co
     hipLaunchKernelGGL(k_planes_raster_rows, dim3(cdiv(v.rows, TAP_ROWS), cdiv(cdiv(n_cols, 32), TAP_TW), T), dim3(256), 0, (hipStream_t)stream, v,
                        n_cols, out, vec);
     SNN_CHECK_LAUNCH("k_planes_raster_rows");
+    return 0;
+}
+
+// ---- readout weight gradients (kernels: snn_wgrad.h) ----
+static int wgrad_shape_ok(long long rows, int n_cols, int NA, int NB) {
+    return rows >= 1 && rows <= 0x7fffffffLL && n_cols >= 1 && n_cols <= 32 * TAP_MAX_WORDS && NA >= 0 && NB >= 0 && NA + NB >= 1 && NA + NB <= WG_MAX_OUT;
+}
+// row slabs of a call: every slab owns at least one tile
+static int wgrad_slabs(long long rows) { return (int)min((rows + WG_ROWS - 1) / WG_ROWS, (long long)WG_MAX_SLABS); }
+
+size_t snn_li_heads_wgrad_workspace_bytes(int64_t rows, int n_cols, int NA, int NB) {
+    if (!wgrad_shape_ok(rows, n_cols, NA, NB)) return 0;
+    return (size_t)wgrad_slabs(rows) * (size_t)(NA + NB) * (size_t)n_cols * sizeof(float);
+}
+
+int snn_li_heads_wgrad(const void* planes, const snn_planes_view* view, int n_cols, int T_prime, const snn_params* p, const float* grad_a,
+                       const float* grad_b, int NA, int NB, float* gw_a, float* gw_b, int accumulate, void* scratch, size_t scratch_bytes,
+                       snn_stream_t stream) {
+    WgradArgs a;
+    if (tap_view("snn_li_heads_wgrad", planes, view, T_prime, &a.v)) return -1;
+    if (!p) return fail(-1, "snn_li_heads_wgrad: null parameters");
+    if (p->li_order != 0 && p->li_order != 1) return fail(-1, "snn_li_heads_wgrad: li_order = %d (0 jump-first, 1 voltage-first)", p->li_order);
+    if (n_cols < 1 || n_cols > 32 * a.v.words) return fail(-1, "snn_li_heads_wgrad: n_cols = %d outside 1 .. 32 x words = %d", n_cols, 32 * a.v.words);
+    if (!wgrad_shape_ok(a.v.rows, n_cols, NA, NB))
+        return fail(-1, "snn_li_heads_wgrad: NA = %d, NB = %d (each >= 0, 1 <= NA + NB <= %d)", NA, NB, WG_MAX_OUT);
+    if ((NA && (!grad_a || !gw_a)) || (NB && (!grad_b || !gw_b))) return fail(-1, "snn_li_heads_wgrad: null gradient or result of a head with outputs");
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "snn_li_heads_wgrad: accumulate = %d (0 or 1)", accumulate);
+    const size_t need = snn_li_heads_wgrad_workspace_bytes(a.v.rows, n_cols, NA, NB);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 3)) return fail(-1, "snn_li_heads_wgrad: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    Kappa kap;
+    li_kappa(p, T_prime, &kap);
+    for (int t = 0; t < SNN_MAX_STEPS; ++t) a.kappa[t] = kap.last[t];
+    a.ga = grad_a; a.gb = grad_b; a.NA = NA; a.NB = NB; a.n_cols = n_cols; a.T = T_prime;
+    a.tiles = cdiv(a.v.rows, WG_ROWS); a.n_slabs = wgrad_slabs(a.v.rows);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_li_wgrad_partial, dim3(a.n_slabs, cdiv(cdiv(n_cols, 32), WG_WORDS), cdiv(NA + NB, WG_JW)), dim3(256), 0, s, a, (float*)scratch);
+    SNN_CHECK_LAUNCH("k_li_wgrad_partial");
+    hipLaunchKernelGGL(k_li_wgrad_reduce, dim3(cdiv((long long)(NA + NB) * n_cols, WG_RED)), dim3(256), 0, s, (const float*)scratch, a.n_slabs, NA, NB, n_cols,
+                       gw_a, gw_b, accumulate);
+    SNN_CHECK_LAUNCH("k_li_wgrad_reduce");
     return 0;
 }
 

@@ -8,7 +8,7 @@ import os
 
 from torch import nn
 
-from . import ops
+from . import ops, readout
 from .rpn import _SpikingHead, _WeightCache, _pack_heads_unchecked, _per_precision
 
 
@@ -45,6 +45,8 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         self.p_lif = ops.LIFParameters(alpha=100, v_th=torch.tensor(0.1))   # :449,452
         self.li_order = "jump_first"
         self.spike_rates = False
+        self.train_readout = False         # True: in grad mode, with cls_score.weight or bbox_pred.weight requiring grad, the outputs of forward /
+                                           # forward_roialign carry a grad_fn to those two weights alone (readout.py); False: as ever
         self.precision = "bf16x3"          # or "f32" (fp32 matrix cores) / "mxfp6" (fp4 x fp6 digit planes) / "bf16" (ONE bf16 weight plane: fc6, fc7
                                            # and the LI heads on w.to(torch.bfloat16) - outside the 1e-4-to-fp32 contract, as "mxfp6"); see RPNHeadSNN
         self.fc6 = nn.Linear(in_channels, representation_size, bias=False)          # :448
@@ -123,17 +125,46 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         self.route_stat = torch.empty(4, dtype=torch.int32, device=dev)
         return dict(fc6_route=route, fc6_crossover=self.fc6_crossover, route_stat=self.route_stat)
 
-    @torch.no_grad()
     def forward(self, x):
+        if self.train_readout and readout.wanted(self, self.cls_score.weight, self.bbox_pred.weight):
+            cls, bbox = self._forward(x)
+            R = int(cls.shape[0])
+            return self._attach_readout(cls, bbox, R, int(x[0].numel()) if R else self.in_channels)
+        return self._forward(x)
+
+    def forward_roialign(self, feats, scales, rois, roi_level, roi_batch=None):
+        """Same head fed straight from the FPN maps: MultiScaleRoIAlign(7x7, sampling 2) is fused with the encoder
+        (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2) - or, with
+        ``roi_batch`` (int32 [R], the image of every row: the table ops.roi_assign writes), rois [R,4]."""
+        if self.train_readout and readout.wanted(self, self.cls_score.weight, self.bbox_pred.weight):
+            cls, bbox = self._forward_roialign(feats, scales, rois, roi_level, roi_batch)
+            return self._attach_readout(cls, bbox, int(cls.shape[0]), int(feats[0].shape[1]) * 49)
+        return self._forward_roialign(feats, scales, rois, roi_level, roi_batch)
+
+    def _attach_readout(self, cls, bbox, R: int, D: int):
+        """the outputs of the pass that just ran, with a grad_fn that leads to cls_score.weight and bbox_pred.weight alone (readout.py;
+        DESIGN.md 4.13): lif7's planes are cloned out of the workspace, backward is snn_li_heads_wgrad at T' = T on the clone"""
+        from . import taps
+        ws = view = p = None
+        T = int(self.num_steps)
+        with torch.no_grad():
+            prec = self._resolve_precision()
+            p = self._params(prec)
+            if R:
+                route = self.fc6_route if self.fc6_route is not None else os.environ.get("SNN_FC6_ROUTE", "sparse")
+                _, view = taps.det_planes_views(R, D, self.representation_size, self.num_classes, int(self.bbox_pred.weight.shape[0]), T, p,
+                                                w6_inner=self.fc6_inner(prec), route=route, spike_rates=False)
+                ws = taps._current_ws(cls.device)
+        return readout.attach(self.cls_score.weight, self.bbox_pred.weight, (cls, bbox), ws, view, self.representation_size, T, p, lambda g: g)
+
+    @torch.no_grad()
+    def _forward(self, x):
         x = x.flatten(start_dim=1)                                     # :473
         out = ops.det_head_forward(x, T=int(self.num_steps), **self._pass_args(x.shape[1], "%d" % x.shape[1]), **self._route_args(x.device))
         return self._finish(out)
 
     @torch.no_grad()
-    def forward_roialign(self, feats, scales, rois, roi_level, roi_batch=None):
-        """Same head fed straight from the FPN maps: MultiScaleRoIAlign(7x7, sampling 2) is fused with the encoder
-        (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2) - or, with
-        ``roi_batch`` (int32 [R], the image of every row: the table ops.roi_assign writes), rois [R,4]."""
+    def _forward_roialign(self, feats, scales, rois, roi_level, roi_batch=None):
         if roi_batch is None:
             rois, roi_batch = rois[:, 1:5], rois[:, 0]
         out = ops.det_head_forward_roialign(feats, scales, rois, roi_batch, roi_level, T=int(self.num_steps),

@@ -1150,6 +1150,14 @@ def pack_padded_detections(out, max_det: int):
     return static.pack_padded_detections(out, max_det)
 
 
+def li_heads_wgrad(planes, view, n_cols: int, T_prime: int, p: snn_params, grad_a, grad_b, out=None, accumulate: bool = False):
+    """exact gradients of the two LI heads' weights from spike planes: (gw_a [NA, n_cols], gw_b [NB, n_cols]) = grad^T x the kappa fold of the
+    first T_prime steps (snn_li_heads_wgrad; deterministic, no host synchronisation).  The call belongs to the readout gradients and is kept
+    with them: readout.li_heads_wgrad, which this name forwards to (as pack_padded_detections forwards to static.py)."""
+    from . import readout
+    return readout.li_heads_wgrad(planes, view, n_cols, T_prime, p, grad_a, grad_b, out=out, accumulate=accumulate)
+
+
 # ---------------------------------------------------------------------------------------------
 # device guard: every wrapper above launches on "the current stream of the current device"; a caller holding tensors on
 # another GPU of the process (cuda:1 while cuda:0 is current) gets that device made current for the call, as torch's

@@ -208,6 +208,21 @@ class RoIHeadsSNN(nn.Module):
             return head.forward_roialign_readouts(feats, scales, rois, lvl, steps)
         return head.forward_readouts(pool(features, proposals, image_shapes), steps)
 
+    def head_outputs(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]]):
+        """the head call of ``forward`` alone: ``(class_logits [R, K], box_regression [R, K4])``, RoIs in the order of ``proposals`` (the
+        fused RoIAlign path where ``forward`` takes it).  With ``train_readout`` on the head, grad mode on and a readout weight requiring
+        grad, the two outputs carry a ``grad_fn`` (readout.py): a caller puts their own loss on them in eval mode and gets the exact
+        gradients of ``cls_score.weight`` / ``bbox_pred.weight``.  ``model.train()`` stays refused."""
+        if self.training:
+            raise NotImplementedError("inference only: training the RoI heads is out of scope (DESIGN.md §7)")
+        pool, head = self.box_roi_pool, self.box_head_and_predictor
+        if getattr(head, "spike_rates", False):
+            raise NotImplementedError("head_outputs: spike-rate mode returns rates, not outputs - use forward()")
+        if self._fuses_roi_align("forward_roialign"):
+            feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
+            return head.forward_roialign(feats, scales, rois, lvl)
+        return head(pool(features, proposals, image_shapes))
+
     def _fuses_roi_align(self, method: str) -> bool:
         """does the head call take the fused RoIAlign path: the head has ``method`` and the pool is the 7x7, sampling-2 RoIAlign
         the fused kernel restates"""

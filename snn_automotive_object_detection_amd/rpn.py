@@ -4,7 +4,8 @@ Same constructor, same ``forward`` signature and return values, same ``state_dic
 (``shared_conv.weight``, ``conv_cls.weight``, ``conv_bbox.weight``) and weight init (rpn.py:78-82);
 ``RegionProposalNetwork.forward`` (rpn.py:613) can call it unchanged.  The spike-rate variant the
 reference keeps in a string literal (rpn.py:126-200, enabled there by editing the source) is the
-attribute ``spike_rates`` here.  Inference only (no autograd through the kernels)."""
+attribute ``spike_rates`` here.  Inference only (no autograd through the kernels) - but for the opt-in
+``train_readout``, which differentiates the outputs with respect to the two readout weights and nothing else (readout.py)."""
 import os
 import threading
 import warnings
@@ -13,7 +14,7 @@ from typing import List, Tuple
 import torch
 from torch import nn, Tensor
 
-from . import ops
+from . import ops, readout
 from ._cache import StreamSafeEntry
 
 
@@ -141,6 +142,9 @@ class RPNHeadSNN(_SpikingHead):
         self.num_anchors = num_anchors
         self.li_order = "jump_first"      # Norse LI update order
         self.spike_rates = False          # True: forward returns the rpn.py:126-200 third value too
+        # True: in grad mode, with conv_cls.weight or conv_bbox.weight requiring grad, forward's outputs carry a grad_fn that gives those two
+        # weights their exact gradients (readout.py).  False (default): forward is what it always was - no grad anywhere
+        self.train_readout = False
         # "bf16x3": bf16 matrix cores with an exact 3-way split of the fp32 weights (default);
         # "f32": fp32 matrix cores with the conv + LIF fused over T.  Both give fp32-exact contractions.
         # "mxfp6": fp4 x fp6 block-scaled matrix path, weights as 6 planes of base-32 digits (exact within 2^5 of the
@@ -212,8 +216,34 @@ class RPNHeadSNN(_SpikingHead):
             pos += n
         return (logits, bbox_reg, rates) if with_rates else (logits, bbox_reg)
 
-    @torch.no_grad()
     def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
+        if self.train_readout and readout.wanted(self, self.conv_cls.weight, self.conv_bbox.weight):
+            return self._forward_train_readout(x)
+        return self._forward(x)
+
+    def _forward_train_readout(self, x: List[Tensor]):
+        """``forward`` - the same launches, the same bits - with a grad_fn on its outputs that leads to conv_cls.weight and conv_bbox.weight
+        alone (readout.py): the shared LIF's planes are cloned out of the workspace, backward brings the per-level NCHW
+        gradients into the [P, A] / [P, 4A] row order and runs snn_li_heads_wgrad at T' = T on the clone"""
+        from . import taps
+        logits, bbox_reg = self._forward(x)
+        with torch.no_grad():
+            C, A, p, _, _ = self._pass_args()
+            shapes = [(int(f.shape[0]), int(f.shape[2]), int(f.shape[3])) for f in x]
+            route = self.conv_route if self.conv_route is not None else os.environ.get("SNN_CONV_ROUTE", "sparse")
+            view = taps.rpn_planes_view(shapes, C, A, int(self.num_steps), p, route=route, spike_rates=False)
+            ws = taps._current_ws(logits[0].device)
+            L = len(shapes)
+
+            def to_rows(grads):
+                dev = next(g.device for g in grads if g is not None)
+                return (None if all(g is None for g in grads[:L]) else readout.rpn_grad_rows(grads[:L], shapes, A, dev),
+                        None if all(g is None for g in grads[L:]) else readout.rpn_grad_rows(grads[L:], shapes, 4 * A, dev))
+        outs = readout.attach(self.conv_cls.weight, self.conv_bbox.weight, list(logits) + list(bbox_reg), ws, view, C, int(self.num_steps), p, to_rows)
+        return list(outs[:L]), list(outs[L:])
+
+    @torch.no_grad()
+    def _forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:
         C, A, p, w_shared, w_heads = self._pass_args()
         route = self.conv_route if self.conv_route is not None else os.environ.get("SNN_CONV_ROUTE", "sparse")
         if route == "sparse":                                         # the plain entry: the launches of every earlier version
