@@ -719,6 +719,62 @@ int snn_li_heads_wgrad(const void* planes, const snn_planes_view* view, int n_co
                        float* gw_a /* [NA][n_cols] */, float* gw_b /* [NB][n_cols] */, int accumulate, void* scratch,
                        size_t scratch_bytes, snn_stream_t stream);
 
+/* ---- readout fine-tuning: target matching and the two head losses with their gradients -----------------------------
+ * What lies between the head outputs and a scalar in the reference's training forward, for the readouts only: the gradients written here
+ * are the `grad_a` / `grad_b` of snn_li_heads_wgrad.  All three calls are stream-only, synchronise nothing, are hipGraph-capturable under
+ * the capture contract above (host tables are read at enqueue time and travel as kernel arguments), use no floating-point atomic and clear
+ * nothing with a memset: every output element, and every scratch element a launch reads, is written by a launch of the same call, so two
+ * calls on the same data are bit-equal whatever scratch and outputs held before.  Bad arguments return -1, a shape beyond a limit -4, both
+ * before any device work and with snn_last_error set; each size query is monotone in every argument and 0 outside the limits.
+ *
+ * snn_match_targets: IoU matching (torchvision's Matcher), labels and BoxCoder.encode for N <= 64 images in one call.
+ *   - boxes [sum B_n][4] (anchors or proposals, x1 y1 x2 y2) with the HOST table box_start[N + 1]; gt_boxes [sum G_n][4] and gt_labels
+ *     [sum G_n] int64 (null: RPN mode) with the HOST table gt_start[N + 1]; both tables start at 0; G_n <= 256 (else -4), fewer than 2^31
+ *     boxes; weights: HOST float[4], the coder's (wx, wy, ww, wh); boxes, gt_boxes and reg_target 16-byte aligned;
+ *   - per box: matched_idx int32 = the index of the image's ground-truth box with the largest IoU (the lowest index on a tie), -1 where
+ *     that IoU < low, -2 where low <= IoU < high (both compared in fp32); with allow_low_quality every box whose IoU with some ground-truth
+ *     box equals that box's maximum over the image's boxes gets its own arg-max back (a ground-truth box that overlaps nothing has maximum 0
+ *     and restores every box with IoU 0 to it: the published behaviour); label int32 = 1 / 0 / -1 in RPN mode, gt_labels[idx] / 0 / -1
+ *     otherwise; reg_target [4] = encode(gt[max(idx, 0)], box).  An image with G_n = 0: matched_idx 0, label 0, the encoding of the zero box
+ *     (-inf in the two log terms);
+ *   - the IoU is formed in fp32 in the operation order of torchvision's box_iou with IEEE division: every decision equals the one torch takes
+ *     on the same fp32 boxes.  Precondition: finite coordinates, x2 >= x1 and y2 >= y1, ground-truth boxes with positive area (an IoU of 0 / 0
+ *     is NaN in torch and never a maximum here);
+ *   - scratch (snn_match_targets_workspace_bytes(sum B_n, N)) is used with allow_low_quality only: three launches, else one.
+ *
+ * snn_rpn_loss_grad: the RPN's compute_loss and its gradient with respect to the head outputs.
+ *   - logits [P][A], deltas [P][4A]: the head's own outputs (rows level-major, then image, y, x; `levels`: N, H, W of each level, feat
+ *     unused); label int32, sampled uint8 and reg_target [4] per anchor in the reference's order (image, level, y, x, a) - what
+ *     snn_match_targets writes for boxes = the images' anchors; the kernel maps between the two orders;
+ *   - n = the number of sampled anchors, counted on the device; loss[0] = mean over the sampled anchors of max(x, 0) - x y + log1p(exp(-|x|)),
+ *     y = label; loss[1] = the smooth-L1 sum (beta 1/9) over the four coordinates of the sampled anchors with label 1, divided by n;
+ *     g_logits [P][A] = (sigmoid(x) - y) / n, g_deltas [P][4A] = (d / beta inside |d| < beta, sign(d) outside) / n, zero where the loss does
+ *     not read; n = 0: NaN losses (torch's) and zero gradients;
+ *   - at most 8 levels, A <= 64, fewer than 2^31 anchors (-4); deltas, reg_target, g_deltas 16-byte aligned; three launches.
+ *
+ * snn_det_loss_grad: fastrcnn_loss and its gradient.
+ *   - logits [R][K], box [R][K4], label [R] int32, reg_target [R][4]; K4 must be 4 K (-1: the loss indexes one box per class); 2 <= K <= 256
+ *     (-4 above); rows with label -1 (or a label that is no class) are left out of both terms and get zero gradients: n = the rows with
+ *     label >= 0; with no such row left out the result is the reference's;
+ *   - loss[0] = mean softmax cross-entropy (maximum subtracted), loss[1] = smooth L1 (beta 1/9, sum) on the four outputs of the row's own
+ *     class for labels > 0, divided by n; g_logits = (softmax - onehot) / n, g_box zero but for those four outputs; three launches.
+ *
+ * Rounding: per-term arithmetic is fp32 (expf, logf, log1pf of the device library), the sums of the losses and the softmax denominators
+ * are carried in fp64 and rounded once: against the same formulas in exact arithmetic on the same fp32 inputs a loss is within 10 x 2^-24
+ * of its value, a gradient element within 8 x 2^-24 / n, a regression target within 8 x 2^-24 of its magnitude plus the conditioning of
+ * the centre difference. */
+size_t snn_match_targets_workspace_bytes(int64_t total_boxes, int N);
+int snn_match_targets(const float* boxes, const int64_t* box_start_host, const float* gt_boxes, const int64_t* gt_labels,
+                      const int64_t* gt_start_host, int N, float high, float low, int allow_low_quality, const float* weights_host,
+                      int32_t* matched_idx, int32_t* label, float* reg_target, void* scratch, size_t scratch_bytes, snn_stream_t stream);
+size_t snn_rpn_loss_grad_workspace_bytes(int64_t anchors /* P x A */);
+int snn_rpn_loss_grad(const snn_rpn_level* levels, int n_levels, int A, int N, const float* logits, const float* deltas,
+                      const int32_t* label, const uint8_t* sampled, const float* reg_target, float* loss /* [2] */, float* g_logits,
+                      float* g_deltas, void* scratch, size_t scratch_bytes, snn_stream_t stream);
+size_t snn_det_loss_grad_workspace_bytes(int R, int K);
+int snn_det_loss_grad(const float* logits, const float* box, const int32_t* label, const float* reg_target, int R, int K, int K4,
+                      float* loss /* [2] */, float* g_logits, float* g_box, void* scratch, size_t scratch_bytes, snn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,17 @@ SYMBOLS = {
     "snn_li_heads_wgrad_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "snn_li_heads_wgrad": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int, C.c_int, C.POINTER(snn_params), C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    # target matching and head losses (losses.py).  match: boxes, box_start (host), gt_boxes, gt_labels, gt_start (host), N, high, low,
+    # allow_low_quality, weights (host), matched_idx, label, reg_target, scratch, its bytes
+    "snn_match_targets_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "snn_match_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float,
+                                    C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
+    # levels, n_levels, A, N, logits, deltas, label, sampled, reg_target, loss, g_logits, g_deltas, scratch, its bytes
+    "snn_rpn_loss_grad_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "snn_rpn_loss_grad": (C.c_int, [C.POINTER(snn_rpn_level), C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, c_stream]),
+    # logits, box, label, reg_target, R, K, K4, loss, g_logits, g_box, scratch, its bytes
+    "snn_det_loss_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "snn_det_loss_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_size_t, c_stream]),
 }
 
 _LIB = None
@@ -226,7 +237,10 @@ _STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_pack_padded
                 # (an A/B library from before the spike taps: taps.py then raises AttributeError)
                 "snn_rpn_head_planes_view", "snn_det_head_planes_view", "snn_planes_counts", "snn_planes_raster_nchw", "snn_planes_raster_rows",
                 # (... from before the readout gradients: readout.py then raises AttributeError)
-                "snn_li_heads_wgrad_workspace_bytes", "snn_li_heads_wgrad")
+                "snn_li_heads_wgrad_workspace_bytes", "snn_li_heads_wgrad",
+                # (... from before the head losses: losses.py then raises AttributeError)
+                "snn_match_targets_workspace_bytes", "snn_match_targets", "snn_rpn_loss_grad_workspace_bytes", "snn_rpn_loss_grad",
+                "snn_det_loss_grad_workspace_bytes", "snn_det_loss_grad")
 
 
 class SnnHipError(RuntimeError):

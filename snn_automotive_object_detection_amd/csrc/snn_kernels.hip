@@ -160,6 +160,7 @@ __global__ void k_pack_heads(const float* __restrict__ wa, int NA, const float* 
 #include "snn_affine.h"
 #include "snn_taps.h"
 #include "snn_wgrad.h"
+#include "snn_loss.h"
 
 // ================================================================================================
 // C ABI
@@ -3295,6 +3296,134 @@ int snn_li_heads_wgrad(const void* planes, const snn_planes_view* view, int n_co
     hipLaunchKernelGGL(k_li_wgrad_reduce, dim3(cdiv((long long)(NA + NB) * n_cols, WG_RED)), dim3(256), 0, s, (const float*)scratch, a.n_slabs, NA, NB, n_cols,
                        gw_a, gw_b, accumulate);
     SNN_CHECK_LAUNCH("k_li_wgrad_reduce");
+    return 0;
+}
+
+// ---- readout fine-tuning: target matching and the two head losses (kernels: snn_loss.h) ----
+static inline int misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+size_t snn_match_targets_workspace_bytes(int64_t total_boxes, int N) {
+    if (N < 1 || N > LS_MAX_IMAGES || total_boxes < 0 || total_boxes > 0x7fffffffLL) return 0;
+    // per-GT maxima of every work-group (at most total / 256 + N of them), then the per-GT maxima of every image
+    return ((size_t)(total_boxes / LS_BLOCK) + 2 * (size_t)N) * LS_MAX_GT * sizeof(uint32_t);
+}
+
+int snn_match_targets(const float* boxes, const int64_t* box_start, const float* gt_boxes, const int64_t* gt_labels, const int64_t* gt_start, int N,
+                      float high, float low, int allow_low_quality, const float* weights, int32_t* matched_idx, int32_t* label, float* reg_target,
+                      void* scratch, size_t scratch_bytes, snn_stream_t stream) {
+    if (!box_start || !gt_start || !weights) return fail(-1, "snn_match_targets: null box_start / gt_start / weights");
+    if (N < 1) return fail(-1, "snn_match_targets: N = %d images", N);
+    if (N > LS_MAX_IMAGES) return fail(-4, "snn_match_targets: N = %d images (max %d)", N, LS_MAX_IMAGES);
+    if (allow_low_quality != 0 && allow_low_quality != 1) return fail(-1, "snn_match_targets: allow_low_quality = %d (0 or 1)", allow_low_quality);
+    if (box_start[0] != 0 || gt_start[0] != 0) return fail(-1, "snn_match_targets: box_start[0] and gt_start[0] must be 0");
+    MatchArgs a;
+    int blocks = 0;
+    for (int n = 0; n < N; ++n) {
+        const int64_t B = box_start[n + 1] - box_start[n], G = gt_start[n + 1] - gt_start[n];
+        if (B < 0 || G < 0) return fail(-1, "snn_match_targets: box_start / gt_start must not decrease (image %d)", n);
+        if (box_start[n + 1] > 0x7fffffffLL) return fail(-4, "snn_match_targets: %lld boxes (max 2^31 - 1)", (long long)box_start[n + 1]);
+        if (G > LS_MAX_GT) return fail(-4, "snn_match_targets: image %d has %lld ground-truth boxes (max %d)", n, (long long)G, LS_MAX_GT);
+        a.box_start[n] = (int)box_start[n]; a.gt_start[n] = (int)gt_start[n]; a.blk_start[n] = blocks;
+        blocks += cdiv(B, LS_BLOCK);
+    }
+    a.box_start[N] = (int)box_start[N]; a.gt_start[N] = (int)gt_start[N]; a.blk_start[N] = blocks;
+    for (int n = N + 1; n <= LS_MAX_IMAGES; ++n) a.box_start[n] = a.gt_start[n] = a.blk_start[n] = 0;
+    const int total = a.box_start[N], total_gt = a.gt_start[N];
+    if (total == 0) return 0;
+    if (!boxes || !matched_idx || !label || !reg_target || (total_gt && !gt_boxes)) return fail(-1, "snn_match_targets: null boxes, ground truth or output");
+    if (misaligned16(boxes) || misaligned16(gt_boxes) || misaligned16(reg_target)) return fail(-1, "snn_match_targets: boxes, gt_boxes and reg_target must be 16-byte aligned");
+    const size_t need = snn_match_targets_workspace_bytes(total, N);
+    if (allow_low_quality && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 3)))
+        return fail(-1, "snn_match_targets: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    a.boxes = (const float4*)boxes; a.gt = (const float4*)gt_boxes; a.gt_labels = (const long long*)gt_labels;
+    a.N = N; a.allow_lq = allow_low_quality; a.high = high; a.low = low;
+    a.wx = weights[0]; a.wy = weights[1]; a.ww = weights[2]; a.wh = weights[3];
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* part = (uint32_t*)scratch;
+    uint32_t* gtmax = part ? part + (size_t)blocks * LS_MAX_GT : nullptr;
+    if (allow_low_quality && total_gt) {
+        hipLaunchKernelGGL(k_match_partial, dim3(blocks), dim3(LS_BLOCK), 0, s, a, part);
+        SNN_CHECK_LAUNCH("k_match_partial");
+        hipLaunchKernelGGL(k_match_gtmax, dim3(N), dim3(LS_BLOCK), 0, s, a, (const uint32_t*)part, gtmax);
+        SNN_CHECK_LAUNCH("k_match_gtmax");
+    }
+    hipLaunchKernelGGL(k_match_finish, dim3(blocks), dim3(LS_BLOCK), 0, s, a, (const uint32_t*)gtmax, matched_idx, label, (float4*)reg_target);
+    SNN_CHECK_LAUNCH("k_match_finish");
+    return 0;
+}
+
+size_t snn_rpn_loss_grad_workspace_bytes(int64_t anchors) {
+    if (anchors < 1 || anchors > 0x7fffffffLL) return 0;
+    return LS_HEADER + (size_t)cdiv(anchors, LS_BLOCK) * 3 * sizeof(double);
+}
+
+int snn_rpn_loss_grad(const snn_rpn_level* levels, int n_levels, int A, int N, const float* logits, const float* deltas, const int32_t* label,
+                      const uint8_t* sampled, const float* reg_target, float* loss, float* g_logits, float* g_deltas, void* scratch,
+                      size_t scratch_bytes, snn_stream_t stream) {
+    if (!levels || !logits || !deltas || !label || !sampled || !reg_target || !loss || !g_logits || !g_deltas)
+        return fail(-1, "snn_rpn_loss_grad: null argument");
+    if (n_levels < 1 || A < 1 || N < 1) return fail(-1, "snn_rpn_loss_grad: n_levels = %d, A = %d, N = %d (each >= 1)", n_levels, A, N);
+    if (n_levels > LS_MAX_LEVELS) return fail(-4, "snn_rpn_loss_grad: %d levels (max %d)", n_levels, LS_MAX_LEVELS);
+    if (A > LS_MAX_A) return fail(-4, "snn_rpn_loss_grad: A = %d anchors per position (max %d)", A, LS_MAX_A);
+    RpnLossArgs a;
+    long long rows = 0, per_image = 0;
+    for (int l = 0; l < LS_MAX_LEVELS; ++l) { a.row_start[l] = 0; a.hw[l] = 1; a.anc_off[l] = 0; }
+    for (int l = 0; l < n_levels; ++l) {
+        if (levels[l].N != N || levels[l].H < 1 || levels[l].W < 1)
+            return fail(-1, "snn_rpn_loss_grad: level %d is %d x %d x %d (N = %d, H and W >= 1)", l, levels[l].N, levels[l].H, levels[l].W, N);
+        const long long hw = (long long)levels[l].H * levels[l].W;
+        if ((rows + hw * N) * A > 0x7fffffffLL) return fail(-4, "snn_rpn_loss_grad: more than 2^31 - 1 anchors");
+        a.row_start[l] = (int)rows; a.hw[l] = (int)hw; a.anc_off[l] = (int)(per_image * A);
+        rows += hw * N; per_image += hw;
+    }
+    a.n_levels = n_levels; a.A = A; a.per_image = (int)(per_image * A); a.total = (int)(rows * A);
+    if (misaligned16(deltas) || misaligned16(reg_target) || misaligned16(g_deltas))
+        return fail(-1, "snn_rpn_loss_grad: deltas, reg_target and g_deltas must be 16-byte aligned");
+    const size_t need = snn_rpn_loss_grad_workspace_bytes(a.total);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 7)) return fail(-1, "snn_rpn_loss_grad: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    int* n_dev = (int*)scratch;
+    double* part = (double*)((char*)scratch + LS_HEADER);
+    const int nb = cdiv(a.total, LS_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_rpn_loss<false>, dim3(nb), dim3(LS_BLOCK), 0, s, a, logits, (const float4*)deltas, label, sampled, (const float4*)reg_target, part,
+                       (const int*)n_dev, g_logits, (float4*)g_deltas);
+    SNN_CHECK_LAUNCH("k_rpn_loss<false>");
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(LS_BLOCK), 0, s, (const double*)part, nb, loss, n_dev);
+    SNN_CHECK_LAUNCH("k_loss_finish");
+    hipLaunchKernelGGL(k_rpn_loss<true>, dim3(nb), dim3(LS_BLOCK), 0, s, a, logits, (const float4*)deltas, label, sampled, (const float4*)reg_target, part,
+                       (const int*)n_dev, g_logits, (float4*)g_deltas);
+    SNN_CHECK_LAUNCH("k_rpn_loss<true>");
+    return 0;
+}
+
+size_t snn_det_loss_grad_workspace_bytes(int R, int K) {
+    if (R < 1 || K < 2 || K > LS_MAX_K || (long long)R * K * 4 > 0x7fffffffLL) return 0;
+    return LS_HEADER + (size_t)cdiv(R, DL_ROWS) * 3 * sizeof(double);
+}
+
+int snn_det_loss_grad(const float* logits, const float* box, const int32_t* label, const float* reg_target, int R, int K, int K4, float* loss,
+                      float* g_logits, float* g_box, void* scratch, size_t scratch_bytes, snn_stream_t stream) {
+    if (!logits || !box || !label || !reg_target || !loss || !g_logits || !g_box) return fail(-1, "snn_det_loss_grad: null argument");
+    if (R < 1 || K < 2) return fail(-1, "snn_det_loss_grad: R = %d rows, K = %d classes (R >= 1, K >= 2)", R, K);
+    if (K4 != 4 * K) return fail(-1, "snn_det_loss_grad: K4 = %d box outputs for K = %d classes (the loss indexes one box per class: K4 = 4 K)", K4, K);
+    if (K > LS_MAX_K) return fail(-4, "snn_det_loss_grad: K = %d classes (max %d)", K, LS_MAX_K);
+    if ((long long)R * K4 > 0x7fffffffLL) return fail(-4, "snn_det_loss_grad: R x 4K = %lld elements (max 2^31 - 1)", (long long)R * K4);
+    if (misaligned16(logits) || misaligned16(box) || misaligned16(reg_target) || misaligned16(g_logits) || misaligned16(g_box))
+        return fail(-1, "snn_det_loss_grad: logits, box, reg_target, g_logits and g_box must be 16-byte aligned");
+    const size_t need = snn_det_loss_grad_workspace_bytes(R, K);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 7)) return fail(-1, "snn_det_loss_grad: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    int* n_dev = (int*)scratch;
+    double* part = (double*)((char*)scratch + LS_HEADER);
+    const int nb = cdiv(R, DL_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_det_loss<false>, dim3(nb), dim3(LS_BLOCK), 0, s, logits, (const float4*)box, label, (const float4*)reg_target, R, K, part,
+                       (const int*)n_dev, g_logits, (float4*)g_box);
+    SNN_CHECK_LAUNCH("k_det_loss<false>");
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(LS_BLOCK), 0, s, (const double*)part, nb, loss, n_dev);
+    SNN_CHECK_LAUNCH("k_loss_finish");
+    hipLaunchKernelGGL(k_det_loss<true>, dim3(nb), dim3(LS_BLOCK), 0, s, logits, (const float4*)box, label, (const float4*)reg_target, R, K, part,
+                       (const int*)n_dev, g_logits, (float4*)g_box);
+    SNN_CHECK_LAUNCH("k_det_loss<true>");
     return 0;
 }
 

@@ -78,6 +78,32 @@ class GeneralizedRCNN(nn.Module):
         detections = self.finish_detections(detections, proposal_extras, images.image_sizes, original_image_sizes)
         return detections, {"rpn": rpn_taps, "det": det_taps}
 
+    def readout_losses(self, images: List[Tensor], targets: List[Dict[str, Tensor]], generator=None) -> Dict[str, Tensor]:
+        """the reference's training forward for the READOUTS (generalized_rcnn.py:60-123 with self.training), in eval mode:
+        transform and backbone under no_grad, then RegionProposalNetwork.head_losses and RoIHeadsSNN.head_losses - target matching and the
+        fused losses on the GPU (losses.py).  Returns the reference's dict: loss_objectness, loss_rpn_box_reg, loss_classifier,
+        loss_box_reg.  With ``train_readout`` on both heads (and readout.freeze_hidden) ``sum(losses.values()).backward()`` gives the four
+        readout weights their exact gradients; nothing else receives one.  Proposals are selected with the "training" entries of the
+        RPN's two top-n dicts.  ``generator``: the torch.Generator of both samplers.  ``forward`` in training mode still raises."""
+        if self.training:
+            raise NotImplementedError("readout_losses runs in eval mode: model.train() is out of scope (DESIGN.md §7)")
+        self.roi_heads.check_targets(targets)
+        for i, t in enumerate(targets):                                             # generalized_rcnn.py:62-77
+            b = t["boxes"]
+            if not isinstance(b, torch.Tensor) or b.dim() != 2 or b.shape[-1] != 4:
+                raise ValueError("Expected target boxes to be a tensor of shape [N, 4], got %s" % (tuple(b.shape) if isinstance(b, torch.Tensor) else type(b),))
+        with torch.no_grad():
+            images, targets = self.transform(images, targets)
+            features = self.backbone(images.tensors)
+            if isinstance(features, torch.Tensor):
+                features = OrderedDict([("0", features)])
+        feats = list(features.values())
+        head_out, losses = self.rpn.head_losses(images, features, targets, generator)
+        with torch.no_grad():
+            proposals, _ = self.rpn.proposals_from_head(images, feats, head_out, top_n="training")
+        losses.update(self.roi_heads.head_losses(features, proposals, images.image_sizes, targets, generator))
+        return {k: losses[k] for k in ("loss_classifier", "loss_box_reg", "loss_objectness", "loss_rpn_box_reg")}
+
     def _resize_ratios(self, image_sizes, original_image_sizes, device) -> Tensor:
         """resize_boxes' ratios (fp32 new / old, as it forms them) of every image as one device tensor; uploaded once per set of sizes"""
         cache = self.__dict__.setdefault("_ratio_cache", {})

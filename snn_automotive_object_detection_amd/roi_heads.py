@@ -31,7 +31,7 @@ class RoIHeadsSNN(nn.Module):
         self.fuse_roi_align = True        # use the fused RoIAlign+encoder kernel when pool/head support it
         self.post = "hip"                 # "hip": snn_det_postprocess; "reference": the reference's order on stock torch ops
         self._warned = set()              # fallback reasons already reported
-        # training-side hyper-parameters are accepted for signature compatibility only
+        # training-side hyper-parameters: read by head_losses alone (the Matcher's thresholds, the sampler's two numbers)
         self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
         self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
         if any(m is not None for m in (mask_roi_pool, mask_head, mask_predictor, keypoint_roi_pool,
@@ -222,6 +222,55 @@ class RoIHeadsSNN(nn.Module):
             feats, scales, rois, lvl = pool.assign(features, proposals, image_shapes)
             return head.forward_roialign(feats, scales, rois, lvl)
         return head(pool(features, proposals, image_shapes))
+
+    def check_targets(self, targets) -> None:
+        """roi_heads.py:1025-1036 and the dtype checks of its forward (1190-1201): boxes float, labels int64"""
+        if targets is None:
+            raise ValueError("targets should not be None")
+        if not all("boxes" in t for t in targets):
+            raise ValueError("Every element of targets should have a boxes key")
+        if not all("labels" in t for t in targets):
+            raise ValueError("Every element of targets should have a labels key")
+        for t in targets:
+            if t["boxes"].dtype not in (torch.float, torch.double, torch.half):
+                raise TypeError("target boxes must of float type, instead got %s" % t["boxes"].dtype)
+            if t["labels"].dtype != torch.int64:
+                raise TypeError("target labels must of int64 type, instead got %s" % t["labels"].dtype)
+
+    def select_training_samples(self, proposals: List[Tensor], targets, generator=None):
+        """roi_heads.py:1037-1073: the ground-truth boxes join the proposals, every box is matched (fg_iou_thresh / bg_iou_thresh, no
+        low-quality matches) and encoded with the coder's weights in ONE losses.match_targets call, the sampler picks
+        batch_size_per_image of them per image.  Returns ``(proposals, matched_idxs, labels, regression_targets)`` of the sampled boxes."""
+        from . import losses
+        self.check_targets(targets)
+        dtype, device = proposals[0].dtype, proposals[0].device
+        gt_boxes = [t["boxes"].to(device=device, dtype=dtype) for t in targets]
+        gt_labels = [t["labels"].to(device) for t in targets]
+        proposals = [torch.cat((p.detach(), g)) for p, g in zip(proposals, gt_boxes)]
+        matched_idxs, labels, regression_targets = losses.match_targets(proposals, gt_boxes, gt_labels, self.fg_iou_thresh, self.bg_iou_thresh, False,
+                                                                        self.box_coder.weights)
+        pos, neg = losses.BalancedPositiveNegativeSampler(self.batch_size_per_image, self.positive_fraction)(labels, generator)
+        out = ([], [], [], [])
+        for i, (p, n) in enumerate(zip(pos, neg)):
+            keep = torch.where(p | n)[0]
+            for dst, src in zip(out, (proposals[i], matched_idxs[i].clamp(min=0), labels[i], regression_targets[i])):
+                dst.append(src[keep])
+        return out
+
+    def head_losses(self, features: Dict[str, Tensor], proposals: List[Tensor], image_shapes: List[Tuple[int, int]], targets, generator=None):
+        """the RoI heads' half of a readout fine-tuning step (roi_heads.py:1203-1245 in eval mode): select_training_samples,
+        ``head_outputs`` on the sampled RoIs and losses.fastrcnn_loss -> {"loss_classifier", "loss_box_reg"}.  With ``train_readout`` on
+        the head the two losses lead to cls_score.weight and bbox_pred.weight through autograd."""
+        from . import losses
+        if self.training:
+            raise NotImplementedError("head_losses runs in eval mode: training the RoI heads is out of scope (DESIGN.md §7)")
+        with torch.no_grad():
+            proposals, _, labels, regression_targets = self.select_training_samples(proposals, targets, generator)
+        class_logits, box_regression = self.head_outputs(features, proposals, image_shapes)
+        if box_regression.shape[-1] != 4 * class_logits.shape[-1]:
+            raise NotImplementedError("head_losses needs one box per class (only_one_bbox heads have no fastrcnn_loss in the reference either)")
+        loss_classifier, loss_box_reg = losses.fastrcnn_loss(class_logits, box_regression, labels, regression_targets)
+        return {"loss_classifier": loss_classifier, "loss_box_reg": loss_box_reg}
 
     def _fuses_roi_align(self, method: str) -> bool:
         """does the head call take the fused RoIAlign path: the head has ``method`` and the pool is the 7x7, sampling-2 RoIAlign

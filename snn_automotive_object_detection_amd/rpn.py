@@ -321,6 +321,10 @@ class RegionProposalNetwork(nn.Module):
         self.anchor_generator = anchor_generator
         self.head = head
         self.box_coder = BoxCoder(weights=(1.0, 1.0, 1.0, 1.0))                       # rpn.py:347
+        # the training-side arguments (rpn.py:350-362) are read by head_losses alone: the Matcher's thresholds (allow_low_quality_matches
+        # = True there) and the sampler's two numbers
+        self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
+        self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
         self._pre_nms_top_n = pre_nms_top_n
         self._post_nms_top_n = post_nms_top_n
         self.nms_thresh = nms_thresh
@@ -338,8 +342,17 @@ class RegionProposalNetwork(nn.Module):
     def post_nms_top_n(self):
         return self._post_nms_top_n["training" if self.training else "testing"]
 
-    def filter_proposals_reference(self, proposals, objectness, image_shapes, num_anchors_per_level):
+    def _top_n(self, top_n=None):
+        """(pre_nms_top_n, post_nms_top_n): ``top_n`` if given ("training" / "testing", or the pair itself), else by ``self.training``"""
+        if top_n is None:
+            return self.pre_nms_top_n(), self.post_nms_top_n()
+        if isinstance(top_n, str):
+            return self._pre_nms_top_n[top_n], self._post_nms_top_n[top_n]
+        return int(top_n[0]), int(top_n[1])
+
+    def filter_proposals_reference(self, proposals, objectness, image_shapes, num_anchors_per_level, top_n=None):
         from .stock import boxes as box_ops
+        pre_n, post_n = self._top_n(top_n)
         num_images = proposals.shape[0]
         device = proposals.device
         objectness = objectness.detach().reshape(num_images, -1)
@@ -347,7 +360,7 @@ class RegionProposalNetwork(nn.Module):
                             for i, n in enumerate(num_anchors_per_level)]).reshape(1, -1).expand_as(objectness)
         idx, offset = [], 0
         for ob in objectness.split(num_anchors_per_level, 1):                         # rpn.py:434-446
-            k = min(self.pre_nms_top_n(), ob.shape[1])
+            k = min(pre_n, ob.shape[1])
             idx.append(ob.topk(k, dim=1)[1] + offset)
             offset += ob.shape[1]
         top = torch.cat(idx, dim=1)
@@ -362,18 +375,19 @@ class RegionProposalNetwork(nn.Module):
             boxes, scores, lvl = boxes[keep], scores[keep], lvl[keep]
             keep = torch.where(scores >= self.score_thresh)[0]
             boxes, scores, lvl = boxes[keep], scores[keep], lvl[keep]
-            keep = box_ops.batched_nms(boxes, scores, lvl, self.nms_thresh)[: self.post_nms_top_n()]
+            keep = box_ops.batched_nms(boxes, scores, lvl, self.nms_thresh)[: post_n]
             final_boxes.append(boxes[keep])
             final_scores.append(scores[keep])
         return final_boxes, final_scores, pre_nms
 
-    def filter_proposals(self, objectness, pred_bbox_deltas, anchors, image_shapes, num_anchors_per_level):
+    def filter_proposals(self, objectness, pred_bbox_deltas, anchors, image_shapes, num_anchors_per_level, top_n=None):
         """rpn.py:420-499 restructured for the GPU: per-level top-k on the logits FIRST, then decode / sigmoid / clip /
         size and score filters on the <= 1000 candidates per level only, all images batched, and one NMS launch for
         the whole batch (category = image x level).  Same proposals as `filter_proposals_reference` (tested); two
         host synchronisations instead of about ten per image."""
         from .stock import boxes as box_ops
         from . import ops
+        pre_n, post_n = self._top_n(top_n)
         num_images = objectness.numel() // sum(num_anchors_per_level)
         device = objectness.device
         n_levels = len(num_anchors_per_level)
@@ -381,7 +395,7 @@ class RegionProposalNetwork(nn.Module):
         deltas = pred_bbox_deltas.detach().reshape(num_images, -1, 4)
         idx, lvl, offset = [], [], 0
         for i, ob in enumerate(objectness.split(num_anchors_per_level, 1)):           # rpn.py:434-446
-            k = min(self.pre_nms_top_n(), ob.shape[1])
+            k = min(pre_n, ob.shape[1])
             idx.append(ob.topk(k, dim=1)[1] + offset)
             lvl.append(torch.full((k,), i, dtype=torch.int64, device=device))
             offset += ob.shape[1]
@@ -403,7 +417,7 @@ class RegionProposalNetwork(nn.Module):
         for i in range(num_images):                  # NMS per image (pairs across images would be wasted IoUs)
             order, kept = ops.nms_keep_mask(boxes[i], scores[i], levels, self.nms_thresh)
             kept = kept & valid[i][order]
-            kept = kept & (kept.cumsum(0) <= self.post_nms_top_n())
+            kept = kept & (kept.cumsum(0) <= post_n)
             keep_sorted.append(kept)
             order_all.append(order)
         keep_sorted = torch.stack(keep_sorted)                                         # [N, K] in score order
@@ -416,7 +430,7 @@ class RegionProposalNetwork(nn.Module):
         final_scores = list(prob[img_of, pick].split(counts))
         return final_boxes, final_scores, pre_nms
 
-    def _hip_proposals_refusal(self, objectness):
+    def _hip_proposals_refusal(self, objectness, top_n=None):
         """the limits of snn_rpn_proposals (csrc/snn_post.h), mirrored so that a configuration outside them takes the
         stock-torch path instead of raising: None if the HIP path can run, else the reason"""
         N, A = objectness[0].shape[0], objectness[0].shape[1]
@@ -430,15 +444,16 @@ class RegionProposalNetwork(nn.Module):
             per_image = int(o.shape[1] * o.shape[2] * o.shape[3])
             if per_image * N > 0x7fffffff or per_image >= (1 << 28):
                 return "level %d holds %d anchors per image (HIP path: < 2^28 per image, < 2^31 per batch)" % (l, per_image)
-        k = sum(min(int(self.pre_nms_top_n()), int(o.shape[1] * o.shape[2] * o.shape[3])) for o in objectness)
+        k = sum(min(int(self._top_n(top_n)[0]), int(o.shape[1] * o.shape[2] * o.shape[3])) for o in objectness)
         if k > 8192:
             return "%d pre-NMS candidates per image (HIP path: <= 8192)" % k
         return None
 
-    def _rpn_proposals(self, objectness, pred_bbox_deltas, images):
+    def _rpn_proposals(self, objectness, pred_bbox_deltas, images, top_n=None):
         """ops.rpn_proposals on the head's outputs: (boxes [N, post, 4], scores, counts [N] int32, pre-NMS boxes, pre-NMS objectness),
         everything in device memory"""
         from . import ops
+        pre_n, post_n = self._top_n(top_n)
         N = objectness[0].shape[0]
         A = objectness[0].shape[1]
         lg, dl, hw, strides = [], [], [], []
@@ -451,12 +466,12 @@ class RegionProposalNetwork(nn.Module):
             hw.append((H, W))
             strides.append((image_size[0] // H, image_size[1] // W))
         return ops.rpn_proposals(
-            lg, dl, hw, strides, self.anchor_generator.cell_anchors, images.image_sizes, self.pre_nms_top_n(),
-            self.post_nms_top_n(), self.nms_thresh, self.score_thresh, self.min_size)
+            lg, dl, hw, strides, self.anchor_generator.cell_anchors, images.image_sizes, pre_n,
+            post_n, self.nms_thresh, self.score_thresh, self.min_size)
 
-    def _proposals_hip(self, objectness, pred_bbox_deltas, images, feats):
+    def _proposals_hip(self, objectness, pred_bbox_deltas, images, feats, top_n=None):
         N = objectness[0].shape[0]
-        boxes, scores, counts, pre_b, pre_p = self._rpn_proposals(objectness, pred_bbox_deltas, images)
+        boxes, scores, counts, pre_b, pre_p = self._rpn_proposals(objectness, pred_bbox_deltas, images, top_n)
         cnt = counts.tolist()                                                          # the one host synchronisation
         final = [boxes[i, :c] for i, c in enumerate(cnt)]
         pre_nms = [{"proposals": pre_b[i], "objectness": pre_p[i]} for i in range(N)]
@@ -487,16 +502,17 @@ class RegionProposalNetwork(nn.Module):
         head_out = self.head(feats)                                                   # rpn.py:613 (608-610 in spike-rate mode)
         return self.proposals_from_head(images, feats, head_out)
 
-    def proposals_from_head(self, images, feats, head_out):
+    def proposals_from_head(self, images, feats, head_out, top_n=None):
         """the part of ``forward`` after the head call (rpn.py:614-701): proposals from the head's outputs; also the per-T_rpn
-        step of sweep.timestep_sweep"""
+        step of sweep.timestep_sweep.  ``top_n``: "training" / "testing" - which entries of the two top-n dicts select (None: by
+        ``self.training``, as the reference does)"""
         objectness, pred_bbox_deltas = head_out[:2]
         # spike-rate mode: the head's third value takes the place of `losses` (rpn.py:698-701, "losses = spike_rates")
         rates = head_out[2] if len(head_out) == 3 else None
         if objectness[0].is_cuda and self.post == "hip":
-            why = self._hip_proposals_refusal(objectness)
+            why = self._hip_proposals_refusal(objectness, top_n)
             if why is None:
-                boxes, pre_nms = self._proposals_hip(objectness, pred_bbox_deltas, images, feats)
+                boxes, pre_nms = self._proposals_hip(objectness, pred_bbox_deltas, images, feats, top_n)
                 return boxes, (pre_nms if rates is None else rates)
             with _WARN_LOCK:                                 # loud, once per reason
                 first = why not in self._warned
@@ -509,9 +525,34 @@ class RegionProposalNetwork(nn.Module):
         objectness, pred_bbox_deltas = concat_box_prediction_layers(objectness, pred_bbox_deltas)
         if objectness.is_cuda and self.post == "batched":
             boxes, scores, pre_nms = self.filter_proposals(objectness, pred_bbox_deltas, anchors, images.image_sizes,
-                                                           num_anchors_per_level)
+                                                           num_anchors_per_level, top_n)
         else:
             proposals = self.box_coder.decode(pred_bbox_deltas.detach(), anchors).view(num_images, -1, 4)
             boxes, scores, pre_nms = self.filter_proposals_reference(proposals, objectness, images.image_sizes,
-                                                                     num_anchors_per_level)
+                                                                     num_anchors_per_level, top_n)
         return boxes, (pre_nms if rates is None else rates)
+
+    def head_losses(self, images, features, targets, generator=None, head_out=None):
+        """the RPN's half of a readout fine-tuning step (rpn.py:670-690 in eval mode): the head, the anchors, their matching
+        against ``targets[i]["boxes"]`` (thresholds fg_iou_thresh / bg_iou_thresh, low-quality matches allowed, coder weights (1, 1, 1, 1)),
+        the sampler (batch_size_per_image, positive_fraction; ``generator``: its torch.Generator) and losses.rpn_loss.  Returns
+        ``(head_out, {"loss_objectness", "loss_rpn_box_reg"})``; with ``train_readout`` on the head the two losses lead to conv_cls.weight
+        and conv_bbox.weight through autograd.  ``head_out``: the outputs of a head call already made on these features."""
+        from . import losses
+        if self.training:
+            raise NotImplementedError("head_losses runs in eval mode: training the RPN is out of scope (DESIGN.md §7)")
+        if getattr(self.head, "spike_rates", False):
+            raise NotImplementedError("head_losses: spike-rate mode returns rates, not outputs to put a loss on")
+        feats = list(features.values())
+        with torch.no_grad():                                                         # (targets first: the sampler's torch.where waits for the device)
+            anchors = self.anchor_generator(images, feats)
+            gt = [t["boxes"].to(anchors[0]) for t in targets]
+            _, labels, regression_targets = losses.match_targets(anchors, gt, None, self.fg_iou_thresh, self.bg_iou_thresh, True,
+                                                                 self.box_coder.weights)
+            pos, neg = losses.BalancedPositiveNegativeSampler(self.batch_size_per_image, self.positive_fraction)(labels, generator)
+            sampled = [p | n for p, n in zip(pos, neg)]
+        if head_out is None:
+            head_out = self.head(feats)
+        objectness, pred_bbox_deltas = head_out[:2]
+        loss_objectness, loss_rpn_box_reg = losses.rpn_loss(objectness, pred_bbox_deltas, labels, regression_targets, sampled)
+        return head_out, {"loss_objectness": loss_objectness, "loss_rpn_box_reg": loss_rpn_box_reg}

@@ -31,7 +31,7 @@ def streams(lib: str) -> dict:
             funcs[cur] = []
         elif cur is not None and line.strip() and not line.startswith("Disassembly"):
             ins = line.split("//")[0].strip()
-            if ins:
+            if ins and ins != "...":              # ("...": llvm-objdump's elision of the zero padding behind a symbol - where the next one starts, not code)
                 funcs[cur].append(ins)
     return funcs
 
