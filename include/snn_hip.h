@@ -775,6 +775,58 @@ size_t snn_det_loss_grad_workspace_bytes(int R, int K);
 int snn_det_loss_grad(const float* logits, const float* box, const int32_t* label, const float* reg_target, int R, int K, int K4,
                       float* loss /* [2] */, float* g_logits, float* g_box, void* scratch, size_t scratch_bytes, snn_stream_t stream);
 
+/* ---- hidden-layer gradients: SuperSpike through lif7 into fc7 ---------------------------------------------------------
+ * The reference's hidden cells are Norse LIFCells with the default method "super": Heaviside forward, grad / (alpha |x| + 1)^2 backward,
+ * x = vd - v_th.  With a = dt_tau_mem, b = neg_dt_tau_syn, th = v_th_lif, one neuron of lif_feed_forward_step is
+ *     vd_t = v_{t-1} + a ((v_leak - v_{t-1}) + i_{t-1})     z_t = H(vd_t - th)     v_t = (1 - z_t) vd_t + z_t v_reset     i_t = (i_{t-1} + b i_{t-1}) + cur_t
+ * from v_{-1} = v_leak, i_{-1} = 0.  cur_t first moves a spike at step t + 1, so a pass of T steps has Tc = T - 1 currents that matter.  The
+ * adjoint, with gz_t = dL/dz_t and (G_v, G_i) the gradient of the state after step t (zero after step T - 1; the reset is differentiated
+ * through z, as Norse's autograd does):
+ *     for t = T - 1 .. 0:   d_cur_t = G_i (t <= T - 2);   s = 1 / (alpha |vd_t - th| + 1)^2;   dz = gz_t + G_v (v_reset - vd_t);
+ *                           dvd = G_v (1 - z_t) + dz s;   G_i = dvd a + G_i (1 + b);   G_v = dvd (1 - a)
+ * and dL/dW[n][k] = sum_{t < Tc} sum_r d_cur_t[r][n] spk_in_t[r][k] for the bias-free linear layer in front.  TEACHER FORCING: z_t is the bit
+ * the forward pass saved, never a fresh comparison - a recomputed current may differ from the fused kernel's in its last bit, which moves
+ * vd_t by an ulp under a surrogate that is continuous in |x|, and flips nothing.
+ * All four entries: stream-only, no host synchronisation, no allocation, hipGraph-capturable under the capture contract above, no
+ * floating-point atomics, nothing cleared by a memset - every output and scratch element that is read is written by a launch of the same
+ * call, so two calls on the same data are bit-equal whatever outputs and scratch held before.  Bad arguments return -1 with snn_last_error
+ * before any device work; the size query is monotone in every argument and 0 outside the limits.
+ *
+ * snn_planes_to_rows: the first T' (1 .. view->steps_formed) steps of a plane set in any of the three layouts -> out [T'][rows][words] in
+ *   SNN_PLANES_ROWS order, bit for bit (padding bits included).  The "save" of a pass's planes (the next pass overwrites the workspace) and
+ *   the [M][Kw] operand of snn_spike_gemm / snn_spike_gemm_bf16x3.  `out` must not overlap the planes.  One launch.
+ *
+ * snn_lif_surrogate_bwd: the adjoint above, one thread per (row, column); d_cur [Tc][R][N] = dL/dcur.
+ *   - cur [Tc][R][ldc] (ldc >= N: the un-fused GEMMs' output), z_rows [Tc + 1][R][ceil(N / 32)]: the layer's OWN spikes of all T = Tc + 1
+ *     steps, rows layout; bits at or above N are never read;
+ *   - the upstream gradient is gz_t + kappa_t gu: gz [Tc + 1][R][N] and gu [R][N] are each nullable (both null: -1); kappa = the impulse
+ *     responses of snn_li_heads_wgrad at T = Tc + 1 in p_host->li_order, formed on the host - gu = g_cls W_cls + g_box W_box is then the
+ *     whole readout's pull on lif7's spikes;
+ *   - alpha finite and >= 0 (0: the straight-through estimator); 1 <= Tc <= SNN_MAX_STEPS - 1, N <= 8192; d_cur must not overlap cur;
+ *   - arithmetic: fp32, in the operation order written above (the build does not contract), IEEE division; no scratch memory, no register
+ *     array: the forward sweep parks vd_{t+1} in d_cur[t], the reverse sweep writes d_cur[t] after step t + 1 has consumed that slot.
+ *     Memory-bound, about 4 Tc R N 4 bytes.  One launch.
+ *
+ * snn_spike_linear_wgrad: gw[n][k] (+)= sum_{t < T'} sum_r d_cur[t][r][n] * bit_t(r, k), the weight gradient of a linear layer fed by spikes.
+ *   - a_rows [T'][rows][ceil(K / 32)] (rows layout: snn_planes_to_rows), d_cur [T'][rows][ldd], N <= ldd < 2^28; K <= 8192, N <= 8192, rows < 2^31,
+ *     T' <= SNN_MAX_STEPS; rows past `rows`, columns past N and bits past K contribute nothing and no word past a row's last word is loaded;
+ *   - runs on v_mfma_f32_32x32x2_f32 with both operands taken straight from global memory (no LDS): the spike operand is 0.0 / 1.0, every
+ *     product is exact, a result is an fp32 fused-multiply-add chain over the rows of a slab;
+ *   - DETERMINISTIC: the T' x rows reduction rows are split into at most 16 slabs (a function of T' x rows alone), partial tiles go to
+ *     `scratch` (snn_spike_linear_wgrad_workspace_bytes = slabs x N x K floats), a second launch adds them in ascending order and writes every
+ *     element of gw [N][K] (accumulate = 0) or adds to it (accumulate = 1);
+ *   - rounding: against exact arithmetic every element is within (T' rows + slabs + 2) 2^-24 sum_{t, r} |d_cur[t][r][n]| bit_t(r, k).
+ *   Two launches. */
+int snn_planes_to_rows(const void* workspace, const snn_planes_view* view, int T_prime, uint32_t* out /* [T'][rows][words] */,
+                       snn_stream_t stream);
+int snn_lif_surrogate_bwd(const float* cur /* [Tc][R][ldc] */, int ldc, const uint32_t* z_rows /* [Tc+1][R][ceil(N/32)] */, int Tc, int R,
+                          int N, const snn_params* p_host, float alpha, const float* gz /* [Tc+1][R][N], nullable */,
+                          const float* gu /* [R][N], nullable */, float* d_cur /* [Tc][R][N] */, snn_stream_t stream);
+size_t snn_spike_linear_wgrad_workspace_bytes(int64_t rows, int K, int N, int T_prime);
+int snn_spike_linear_wgrad(const uint32_t* a_rows /* [T'][rows][ceil(K/32)] */, const float* d_cur /* [T'][rows][ldd] */, int ldd,
+                           int T_prime, int64_t rows, int K, int N, float* gw /* [N][K] */, int accumulate, void* scratch,
+                           size_t scratch_bytes, snn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,14 @@ SYMBOLS = {
     # logits, box, label, reg_target, R, K, K4, loss, g_logits, g_box, scratch, its bytes
     "snn_det_loss_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "snn_det_loss_grad": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_size_t, c_stream]),
+    # hidden-layer gradients of fc7 -> lif7 (hidden.py).  planes_to_rows: workspace + view, T', out.  lif_surrogate_bwd: cur, ldc, z_rows, Tc, R, N,
+    # params, alpha, gz, gu, d_cur.  spike_linear_wgrad: a_rows, d_cur, ldd, T', rows, K, N, gw, accumulate, scratch, its bytes
+    "snn_planes_to_rows": (C.c_int, [C.c_void_p, C.POINTER(snn_planes_view), C.c_int, C.c_void_p, c_stream]),
+    "snn_lif_surrogate_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(snn_params), C.c_float, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, c_stream]),
+    "snn_spike_linear_wgrad_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "snn_spike_linear_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_size_t, c_stream]),
 }
 
 _LIB = None
@@ -240,7 +248,9 @@ _STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_pack_padded
                 "snn_li_heads_wgrad_workspace_bytes", "snn_li_heads_wgrad",
                 # (... from before the head losses: losses.py then raises AttributeError)
                 "snn_match_targets_workspace_bytes", "snn_match_targets", "snn_rpn_loss_grad_workspace_bytes", "snn_rpn_loss_grad",
-                "snn_det_loss_grad_workspace_bytes", "snn_det_loss_grad")
+                "snn_det_loss_grad_workspace_bytes", "snn_det_loss_grad",
+                # (... from before the hidden-layer gradients: hidden.py then raises AttributeError)
+                "snn_planes_to_rows", "snn_lif_surrogate_bwd", "snn_spike_linear_wgrad_workspace_bytes", "snn_spike_linear_wgrad")
 
 
 class SnnHipError(RuntimeError):

@@ -161,6 +161,7 @@ __global__ void k_pack_heads(const float* __restrict__ wa, int NA, const float* 
 #include "snn_taps.h"
 #include "snn_wgrad.h"
 #include "snn_loss.h"
+#include "snn_hidden.h"
 
 // ================================================================================================
 // C ABI
@@ -3424,6 +3425,79 @@ int snn_det_loss_grad(const float* logits, const float* box, const int32_t* labe
     hipLaunchKernelGGL(k_det_loss<true>, dim3(nb), dim3(LS_BLOCK), 0, s, logits, (const float4*)box, label, (const float4*)reg_target, R, K, part,
                        (const int*)n_dev, g_logits, (float4*)g_box);
     SNN_CHECK_LAUNCH("k_det_loss<true>");
+    return 0;
+}
+
+// ---- hidden-layer gradients of fc7 -> lif7: SuperSpike LIF adjoint and the spike-fed linear layer's weight gradient (DESIGN.md 4.15;
+// kernels: snn_hidden.h) ----
+static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
+
+int snn_planes_to_rows(const void* ws, const snn_planes_view* view, int T_prime, uint32_t* out, snn_stream_t stream) {
+    TapView v;
+    if (tap_view("snn_planes_to_rows", ws, view, T_prime, &v)) return -1;
+    if (!out) return fail(-1, "snn_planes_to_rows: null result");
+    const long long total = (long long)T_prime * v.rows * v.words;
+    hipLaunchKernelGGL(k_planes_to_rows, dim3((unsigned)min(cdivll(total, 256), 65536LL)), dim3(256), 0, (hipStream_t)stream, v, T_prime, out);
+    SNN_CHECK_LAUNCH("k_planes_to_rows");
+    return 0;
+}
+
+int snn_lif_surrogate_bwd(const float* cur, int ldc, const uint32_t* z_rows, int Tc, int R, int N, const snn_params* p, float alpha, const float* gz,
+                          const float* gu, float* d_cur, snn_stream_t stream) {
+    if (!cur || !z_rows || !d_cur || !p) return fail(-1, "snn_lif_surrogate_bwd: null currents, planes, result or parameters");
+    if (!gz && !gu) return fail(-1, "snn_lif_surrogate_bwd: gz and gu are both null (no upstream gradient)");
+    if (Tc < 1 || Tc > SNN_MAX_STEPS - 1) return fail(-1, "snn_lif_surrogate_bwd: Tc = %d outside [1, %d]", Tc, SNN_MAX_STEPS - 1);
+    if (R < 1 || N < 1 || N > HB_MAX_N || ldc < N) return fail(-1, "snn_lif_surrogate_bwd: R = %d, N = %d, ldc = %d (R >= 1, 1 <= N <= %d, ldc >= N)", R, N, ldc, HB_MAX_N);
+    if (!(alpha >= 0.0f) || !__builtin_isfinite(alpha)) return fail(-1, "snn_lif_surrogate_bwd: alpha = %g (finite and >= 0)", (double)alpha);
+    if (p->li_order != 0 && p->li_order != 1) return fail(-1, "snn_lif_surrogate_bwd: li_order = %d (0 jump-first, 1 voltage-first)", p->li_order);
+    LifBwdArgs a;
+    a.cur = cur; a.z = z_rows; a.gz = gz; a.gu = gu; a.d_cur = d_cur;
+    a.ldc = ldc; a.Tc = Tc; a.R = R; a.N = N; a.Nw = cdiv(N, 32);
+    a.a = p->dt_tau_mem; a.b = p->neg_dt_tau_syn; a.v_leak = p->v_leak; a.v_reset = p->v_reset; a.th = p->v_th_lif; a.alpha = alpha;
+    Kappa kap;
+    li_kappa(p, Tc + 1, &kap);
+    for (int t = 0; t < SNN_MAX_STEPS; ++t) a.kappa[t] = kap.last[t];
+    hipLaunchKernelGGL(k_lif_surrogate_bwd, dim3((unsigned)min(cdivll((long long)R * N, 256), 1LL << 20)), dim3(256), 0, (hipStream_t)stream, a);
+    SNN_CHECK_LAUNCH("k_lif_surrogate_bwd");
+    return 0;
+}
+
+static int spike_wgrad_shape_ok(long long rows, int K, int N, int T) {
+    return rows >= 1 && rows <= 0x7fffffffLL && K >= 1 && K <= SW_MAX_DIM && N >= 1 && N <= SW_MAX_DIM && T >= 1 && T <= SNN_MAX_STEPS;
+}
+// row slabs of the reduction over M = T' x rows: a function of M alone; every slab but the last holds slab_rows rows (a multiple of the batch)
+static int spike_wgrad_slabs(long long M, long long* slab_rows) {
+    const long long want = min(cdivll(M, SW_SLAB_ROWS), (long long)SW_MAX_SLABS);
+    const long long per = cdivll(cdivll(M, want), SW_BATCH) * SW_BATCH;
+    if (slab_rows) *slab_rows = per;
+    return (int)cdivll(M, per);
+}
+
+size_t snn_spike_linear_wgrad_workspace_bytes(int64_t rows, int K, int N, int T_prime) {
+    if (!spike_wgrad_shape_ok(rows, K, N, T_prime)) return 0;
+    return (size_t)spike_wgrad_slabs((long long)rows * T_prime, nullptr) * (size_t)N * (size_t)K * sizeof(float);
+}
+
+int snn_spike_linear_wgrad(const uint32_t* a_rows, const float* d_cur, int ldd, int T_prime, int64_t rows, int K, int N, float* gw, int accumulate,
+                           void* scratch, size_t scratch_bytes, snn_stream_t stream) {
+    if (!a_rows || !d_cur || !gw) return fail(-1, "snn_spike_linear_wgrad: null planes, gradient or result");
+    if (!spike_wgrad_shape_ok(rows, K, N, T_prime))
+        return fail(-1, "snn_spike_linear_wgrad: rows = %lld, K = %d, N = %d, T' = %d (1 <= rows < 2^31, 1 <= K, N <= %d, 1 <= T' <= %d)", (long long)rows, K, N,
+                    T_prime, SW_MAX_DIM, SNN_MAX_STEPS);
+    if (ldd < N || ldd >= (1 << 28)) return fail(-1, "snn_spike_linear_wgrad: ldd = %d (N = %d <= ldd < 2^28)", ldd, N);
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "snn_spike_linear_wgrad: accumulate = %d (0 or 1)", accumulate);
+    const size_t need = snn_spike_linear_wgrad_workspace_bytes(rows, K, N, T_prime);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 3)) return fail(-1, "snn_spike_linear_wgrad: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    SpikeWgradArgs a;
+    a.a = a_rows; a.d = d_cur; a.M = (long long)rows * T_prime; a.ldd = ldd; a.K = K; a.Kw = cdiv(K, 32); a.N = N;
+    a.n_slabs = spike_wgrad_slabs(a.M, &a.slab_rows);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_spike_wgrad_partial, dim3(cdiv(K, SW_TK), cdiv(N, SW_TN), a.n_slabs), dim3(256), 0, s, a, (float*)scratch);
+    SNN_CHECK_LAUNCH("k_spike_wgrad_partial");
+    const size_t n = (size_t)N * K;
+    hipLaunchKernelGGL(k_spike_wgrad_reduce, dim3((unsigned)min(cdivll((long long)n, 256), 1LL << 20)), dim3(256), 0, s, (const float*)scratch, a.n_slabs, n, gw,
+                       accumulate);
+    SNN_CHECK_LAUNCH("k_spike_wgrad_reduce");
     return 0;
 }
 

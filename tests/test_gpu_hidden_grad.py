@@ -1,0 +1,491 @@
+"""Hidden-layer gradients on the GPU: SuperSpike through lif7 into fc7 (include/snn_hip.h: snn_planes_to_rows, snn_lif_surrogate_bwd,
+snn_spike_linear_wgrad).
+
+  1. planes_to_rows      bit-equal to the numpy index arithmetic of tests/_taps.py on all three layouts, behind an offset, with a step stride
+                         beyond a plane, into a destination pre-filled with 0xff
+  2. lif_surrogate_bwd   against the fp64 restatement of tests/_hidden_grad.py on the same fp32 currents, planes and upstream gradients; the
+                         tolerance is MEASURED per case: 4 x the error of the op-for-op fp32 CPU evaluation (largest and rms); then the exact
+                         parts: causality, row independence, scaling by 2, padding bits, run to run on a NaN destination
+  3. spike_linear_wgrad  an integer grid whose sums are exact in every order -> bit equality with the float64 expectation; accumulate; poisoned
+                         scratch; run to run; N(0, 1) gradients inside the header's bound
+  4. the module          train_fc7 on dyadic fc6 / fc7 (zero flips by construction; the tapped rasters must equal the oracle's): outputs and
+                         readout gradients bit-equal to the existing paths, fc7.weight.grad against fp64 autograd under the same 4 x rule
+  5. graph capture       the whole chain captured once, replayed on a second input set
+  6. end to end          one fine-tuning step of the small model through readout_losses"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _graph_capture as GC
+from tests import _hidden_grad as HG
+from tests import _taps as TP
+
+pytestmark = pytest.mark.gpu
+RATIOS = {}                       # what the file logs: the largest observed error / tolerance ratios
+
+
+def _L():
+    from snn_automotive_object_detection_amd import _lib
+    return _lib
+
+
+def _params(c: HG.Consts, li_order="jump_first"):
+    L = _L()
+    return L.snn_params(c.a, c.b, c.v_leak, c.v_reset, 0.25, c.th, {"jump_first": 0, "voltage_first": 1}[li_order], L.PRECISIONS["bf16x3"])
+
+
+def _note(key, value):
+    RATIOS[key] = max(RATIOS.get(key, 0.0), float(value))
+
+
+# ---- 1. planes_to_rows -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", (1, 63, 64, 65, 130))
+@pytest.mark.parametrize("layout", TP.LAYOUTS)
+def test_planes_to_rows_is_the_index_arithmetic_of_the_layouts(gpu_device, layout, rows):
+    from snn_automotive_object_detection_amd import hidden
+    L = _L()
+    lib = L.load()
+    rng = np.random.default_rng([layout, rows])
+    for words in (1, 4, 8):
+        if layout == TP.SPLIT4 and words % 4:
+            continue
+        for Tp in (1, 3):
+            steps, offset, stride = Tp + 1, 132, rows * words + 7
+            want = rng.integers(0, 2 ** 32, size=(steps, rows, words), dtype=np.uint64).astype(np.uint32)
+            flat = np.full(offset // 4 + steps * stride, 0xa5a5a5a5, dtype=np.uint32)
+            idx = TP.word_index(layout, rows, words)
+            for t in range(steps):
+                flat[offset // 4 + t * stride + idx] = want[t]
+            assert np.array_equal(TP.rows_from_layout(flat[offset // 4:], steps, rows, words, layout, stride), want)
+            ws = torch.from_numpy(flat.view(np.uint8).copy()).to(gpu_device)
+            view = L.snn_planes_view(offset, stride, rows, words, layout, steps, 0)
+            out = torch.full((Tp, rows, words), -1, dtype=torch.int32, device=gpu_device)                      # 0xff
+            L.check(lib.snn_planes_to_rows(C.c_void_p(ws.data_ptr()), C.byref(view), Tp, C.c_void_p(out.data_ptr()),
+                                           torch.cuda.current_stream().cuda_stream), "snn_planes_to_rows")
+            got = out.cpu().numpy().view(np.uint32)
+            assert np.array_equal(got, want[:Tp]), (layout, rows, words, Tp)
+            assert torch.equal(hidden.planes_to_rows(ws, view, Tp), out)                                        # the wrapper is that call
+    with pytest.raises(L.SnnHipError, match="snn_planes_to_rows"):
+        hidden.planes_to_rows(ws, view, steps + 1)
+
+
+# ---- 2. lif_surrogate_bwd ----------------------------------------------------------------------------------------------------------------------
+LIF_R, LIF_N, LIF_TC = (1, 37, 130), (32, 40, 96), (1, 2, 7, 11, 31)
+ALPHAS, MODES, RATES = (100.0, 1.0, 0.0), ("gz", "gu", "both"), (0.1, 0.5)
+
+
+def _lif_grid():
+    """every (R, N, Tc); the order, the upstream form, alpha, the constants and the spike rate dealt round-robin on strides that do not divide
+    each other, so that every value of each meets every value of the others somewhere"""
+    out, i = [], 0
+    for R in LIF_R:
+        for N in LIF_N:
+            for Tc in LIF_TC:
+                out.append((R, N, Tc, ("jump_first", "voltage_first")[i % 2], MODES[(i // 2) % 3], ALPHAS[(i // 3) % 3],
+                            ("reference", "other")[(i // 5) % 2], RATES[(i // 7) % 2]))
+                i += 1
+    return out
+
+
+def _lif_case(R, N, Tc, order, mode, alpha, cname, rate, dev, scale_gz=1.0):
+    c = HG.REFERENCE if cname == "reference" else HG.OTHER
+    ldc = N + 32 - N % 32 if N % 32 else N + 32                     # ldc > N, padding columns hold NaN
+    cur = HG.draw_currents(Tc, R, N, ldc, rate, c, [R, N, Tc, int(rate * 10)])
+    z = HG.lif_forward(cur[:, :, :N].double(), c)                    # the planes come from an fp64 forward of those currents
+    g = torch.Generator().manual_seed(R * 1000 + N * 10 + Tc)
+    gz = torch.randn((Tc + 1, R, N), generator=g) * scale_gz if mode in ("gz", "both") else None
+    gu = torch.randn((R, N), generator=g) if mode in ("gu", "both") else None
+    return dict(c=c, cur=cur, z=z, gz=gz, gu=gu, order=order, alpha=alpha, N=N, p=_params(c, order), dev=dev)
+
+
+def _run_lif(k, z_rows=None, out=None):
+    from snn_automotive_object_detection_amd import hidden
+    dev = k["dev"]
+    zr = HG.pack_bits(k["z"]) if z_rows is None else z_rows
+    return hidden.lif_surrogate_bwd(k["cur"].to(dev), zr.to(dev), k["N"], k["p"], k["alpha"], gz=None if k["gz"] is None else k["gz"].to(dev),
+                                    gu=None if k["gu"] is None else k["gu"].to(dev), out=out)
+
+
+def _ref_lif(k, dtype):
+    Tc = k["cur"].shape[0]
+    return HG.adjoint(k["cur"][:, :, :k["N"]], k["z"], k["c"], k["alpha"], gz=k["gz"], gu=k["gu"],
+                      kappa=HG.kappa(k["c"], Tc + 1, k["order"], dtype), dtype=dtype)
+
+
+@pytest.mark.parametrize("R,N,Tc,order,mode,alpha,cname,rate", _lif_grid(),
+                         ids=["R%d_N%d_Tc%d_%s_%s_a%g_%s_r%g" % (g[0], g[1], g[2], g[3][0], g[4], g[5], g[6][0], g[7]) for g in _lif_grid()])
+def test_lif_surrogate_bwd_against_fp64_within_four_times_the_fp32_cpu_error(gpu_device, R, N, Tc, order, mode, alpha, cname, rate):
+    k = _lif_case(R, N, Tc, order, mode, alpha, cname, rate, gpu_device)
+    rate_seen = float(k["z"][1:].float().mean())
+    assert R * N < 64 or abs(rate_seen - rate) < 0.25 * rate, "spike rate %.3f, wanted about %g" % (rate_seen, rate)
+    ref64, ref32 = _ref_lif(k, torch.float64), _ref_lif(k, torch.float32)
+    got = _run_lif(k).cpu()
+    assert got.shape == ref64.shape and bool(torch.isfinite(got).all())
+    # (voltage-first: a spike of the last step reaches no output, kappa_{T-1} = 0 - with Tc = 1 and gu alone nothing arrives at cur_0)
+    assert float(ref64.abs().max()) > 0 or (Tc == 1 and order == "voltage_first" and mode == "gu")
+    (gmax, grms), (cmax, crms) = HG.errors(got, ref64), HG.errors(ref32, ref64)
+    r_max, r_rms = gmax / (4 * cmax) if cmax else float(gmax > 0), grms / (4 * crms) if crms else float(grms > 0)
+    _note("lif_surrogate_bwd", max(r_max, r_rms))
+    print("lif_surrogate_bwd R %d N %d Tc %d: |err| max %.3g rms %.3g; fp32 CPU %.3g / %.3g; error / tolerance %.3f (max) %.3f (rms); worst so far %.3f"
+          % (R, N, Tc, gmax, grms, cmax, crms, r_max, r_rms, RATIOS["lif_surrogate_bwd"]))
+    assert gmax <= 4 * cmax and grms <= 4 * crms
+
+
+def test_lif_surrogate_bwd_exact_parts(gpu_device):
+    dev = gpu_device
+    for (R, N, Tc, order, mode) in ((37, 40, 11, "jump_first", "both"), (130, 96, 7, "voltage_first", "gz")):
+        k = _lif_case(R, N, Tc, order, mode, 100.0, "other", 0.5, dev)
+        base = _run_lif(k).cpu()
+        # two calls, the second into a destination pre-filled with NaN
+        again = _run_lif(k, out=torch.full((Tc, R, N), float("nan"), device=dev)).cpu()
+        assert torch.equal(base.view(torch.int32), again.view(torch.int32)), "two calls on the same data differ"
+        # bits at or above N, when set, change nothing
+        padded = _run_lif(k, z_rows=HG.pack_bits(k["z"], set_padding=True)).cpu()
+        assert N % 32 == 0 or not torch.equal(HG.pack_bits(k["z"], True), HG.pack_bits(k["z"]))
+        assert torch.equal(base.view(torch.int32), padded.view(torch.int32)), "padding bits were read"
+        # scaling the upstream gradient by 2 scales d_cur by 2, bit for bit
+        k2 = dict(k, gz=k["gz"] * 2.0, gu=None if k["gu"] is None else k["gu"] * 2.0)
+        assert torch.equal((_run_lif(k2).cpu()).view(torch.int32), (base * 2.0).view(torch.int32)), "the adjoint is not linear in its upstream gradient"
+        # a row's result does not depend on any other row's inputs
+        r0 = R // 2
+        other = _lif_case(R, N, Tc, order, mode, 100.0, "other", 0.1, dev)
+        mixed = dict(k, cur=other["cur"].clone(), z=other["z"].clone(), gz=other["gz"] * 3.0, gu=None if k["gu"] is None else other["gu"] - 1.0)
+        mixed["cur"][:, r0], mixed["z"][:, r0], mixed["gz"][:, r0] = k["cur"][:, r0], k["z"][:, r0], k["gz"][:, r0]
+        if k["gu"] is not None:
+            mixed["gu"][r0] = k["gu"][r0]
+        got = _run_lif(mixed).cpu()
+        assert torch.equal(got[:, r0].view(torch.int32), base[:, r0].view(torch.int32)), "row %d depends on other rows" % r0
+        assert not torch.equal(got, base)
+        # causality: an upstream gradient at step t alone leaves d_cur_s == 0 exactly for every s >= t
+        for t in (0, 1, Tc // 2, Tc):
+            gz = torch.zeros_like(k["gz"])
+            gz[t] = k["gz"][t]
+            got = _run_lif(dict(k, gz=gz, gu=None)).cpu()
+            assert not got[t:].any(), "step %d's gradient reached a current of a step >= %d" % (t, t)
+            assert t < 2 or bool(got[:t].any())
+
+
+def test_lif_surrogate_bwd_needs_an_upstream_gradient(gpu_device):
+    from snn_automotive_object_detection_amd import hidden
+    k = _lif_case(7, 40, 2, "jump_first", "gz", 100.0, "reference", 0.5, gpu_device)
+    with pytest.raises(_L().SnnHipError, match="snn_lif_surrogate_bwd"):
+        hidden.lif_surrogate_bwd(k["cur"].to(gpu_device), HG.pack_bits(k["z"]).to(gpu_device), 40, k["p"], 100.0)
+
+
+# ---- 3. spike_linear_wgrad -----------------------------------------------------------------------------------------------------------------------
+W_ROWS, W_DIMS, W_T = (1, 63, 64, 65, 1031), (32, 96, 160), (1, 3, 11)
+DENSITIES = (0.02, 0.3, 1.0)
+
+
+def _spike_rows(Tp, rows, K, density, rng):
+    """(int32 [T', rows, ceil(K / 32)] with the padding bits SET, float64 [T' rows, K])"""
+    z = torch.from_numpy(rng.random((Tp, rows, K)) < density)
+    return HG.pack_bits(z, set_padding=True), z.reshape(Tp * rows, K).double().numpy()
+
+
+def _padded(d: torch.Tensor, ldd: int) -> torch.Tensor:
+    out = torch.full(d.shape[:2] + (ldd,), float("nan"), dtype=torch.float32)
+    out[:, :, :d.shape[2]] = d
+    return out
+
+
+def _poison_wgrad_scratch(dev, rows, K, N, Tp, pattern):
+    from snn_automotive_object_detection_amd import hidden
+    need = _L().load().snn_spike_linear_wgrad_workspace_bytes(rows, K, N, Tp)
+    assert need > 0
+    buf = hidden._WS_WGRAD.get(dev, max(16, need))
+    if pattern == "ff":
+        buf.fill_(0xff)
+    else:
+        buf.view(torch.float32).fill_(float("nan"))                    # the quiet NaN 0x7fc00000
+    return need // (4 * N * K)
+
+
+def _exact_wgrad(dev, rows, K, N, Tp, density, acc, pattern, seed):
+    from snn_automotive_object_detection_amd import hidden
+    rng = np.random.default_rng(seed)
+    a_rows, bits = _spike_rows(Tp, rows, K, density, rng)
+    units = rng.integers(-128, 129, size=(Tp, rows, N))
+    assert Tp * rows * 128 + 64 < 2 ** 24                            # every sum, in any order, stays below 2^24 units of 2^-10
+    d = torch.from_numpy((units * 2.0 ** -10).astype(np.float32))
+    want = units.reshape(Tp * rows, N).astype(np.float64).T @ bits    # exact in float64
+    prior = rng.integers(-64, 65, size=(N, K)).astype(np.float64)
+    out = torch.from_numpy((prior * 2.0 ** -10).astype(np.float32)).to(dev) if acc else torch.full((N, K), float("nan"), device=dev)
+    if acc:
+        want = want + prior
+    want32 = (want * 2.0 ** -10).astype(np.float32)
+    assert np.array_equal(want32.astype(np.float64), want * 2.0 ** -10)
+    _poison_wgrad_scratch(dev, rows, K, N, Tp, pattern)
+    ar, dd = a_rows.to(dev), _padded(d, N + 5).to(dev)
+    got = hidden.spike_linear_wgrad(ar, dd, K, N, out=out, accumulate=bool(acc)).cpu().numpy()
+    bad = got != want32
+    assert not bad.any(), "rows %d K %d N %d T' %d: %d of %d elements differ, the first at %s: %r against %r" % (
+        rows, K, N, Tp, bad.sum(), bad.size, tuple(np.argwhere(bad)[0]), got[bad][0], want32[bad][0])
+    assert np.abs(want32).max() > 0
+    if not acc:                                                      # a second call from another scratch pattern: the same bits
+        _poison_wgrad_scratch(dev, rows, K, N, Tp, "nan" if pattern == "ff" else "ff")
+        again = hidden.spike_linear_wgrad(ar, dd, K, N).cpu().numpy()
+        assert np.array_equal(again.view(np.uint32), got.view(np.uint32)), "two calls on the same data differ"
+
+
+@pytest.mark.parametrize("Tp", W_T)
+@pytest.mark.parametrize("rows", W_ROWS)
+def test_spike_linear_wgrad_is_bit_equal_to_the_integer_expectation(gpu_device, rows, Tp):
+    i = W_ROWS.index(rows) * 3 + W_T.index(Tp)
+    for K in W_DIMS:
+        for N in W_DIMS:
+            _exact_wgrad(gpu_device, rows, K, N, Tp, DENSITIES[i % 3], (i // 2) % 2, ("ff", "nan")[(i // 3) % 2], [rows, Tp, K, N])
+            i += 1
+
+
+@pytest.mark.parametrize("acc", (0, 1))
+def test_spike_linear_wgrad_exact_at_the_fc7_width(gpu_device, acc):
+    _exact_wgrad(gpu_device, 257, 1024, 1024, 11, 0.3, acc, "ff", [257, 1024, acc])
+
+
+@pytest.mark.parametrize("rows,K,N,Tp", ((65, 96, 160, 3), (1031, 160, 96, 11), (257, 1024, 1024, 11)))
+def test_spike_linear_wgrad_stays_inside_the_headers_bound(gpu_device, rows, K, N, Tp):
+    from snn_automotive_object_detection_amd import hidden
+    rng = np.random.default_rng([rows, K, N, Tp, 7])
+    a_rows, bits = _spike_rows(Tp, rows, K, 0.3, rng)
+    d = torch.from_numpy(rng.standard_normal((Tp, rows, N)).astype(np.float32))
+    d64 = d.reshape(Tp * rows, N).double().numpy()
+    want = d64.T @ bits
+    slabs = _poison_wgrad_scratch(gpu_device, rows, K, N, Tp, "ff")
+    tol = (Tp * rows + slabs + 2) * 2.0 ** -24 * (np.abs(d64).T @ bits)
+    got = hidden.spike_linear_wgrad(a_rows.to(gpu_device), _padded(d, N + 32).to(gpu_device), K, N).cpu().numpy().astype(np.float64)
+    err = np.abs(got - want)
+    worst = float((err / np.maximum(tol, 1e-300)).max())
+    _note("spike_linear_wgrad bound", worst)
+    print("spike_linear_wgrad rows %d K %d N %d T' %d (%d slabs): largest error / bound = %.4f" % (rows, K, N, Tp, slabs, worst))
+    assert np.isfinite(got).all() and (err <= tol).all() and np.abs(want).max() > 0
+
+
+# ---- 4. the module --------------------------------------------------------------------------------------------------------------------------------
+C_IN, HD, KCLS = 32, 64, 5
+
+
+def _li_torch(z, w, c: HG.Consts, order, dtype):
+    """the LI readout of tests/_planes.li_fp64 in torch (differentiable): spikes [T, R, Hd], weights [n, Hd] -> last membrane [R, n]"""
+    a, b = torch.tensor(c.a, dtype=dtype), torch.tensor(-c.b, dtype=dtype)
+    v = torch.zeros((z.shape[1], w.shape[0]), dtype=dtype)
+    i = torch.zeros_like(v)
+    for t in range(z.shape[0]):
+        cur = z[t] @ w.t()
+        if order == "jump_first":
+            i = i + cur; v = v + a * (i - v); i = i - b * i
+        else:
+            v = v + a * (i - v); i = i - b * i + cur
+    return v
+
+
+def _loss_of(kind, labels, targets):
+    from tests import _head_losses as HL
+    if kind == "quadratic":
+        return lambda cls, box: 0.5 * (cls * cls).sum() + 0.25 * (box * box).sum()
+    return lambda cls, box: sum(HL.det_loss(cls, box, labels, targets.to(box.dtype)))
+
+
+def _cpu_fc7_grad(spk6, spk7, w7, w_cls, w_box, T, order, loss, dtype):
+    """autograd on the CPU in `dtype`: the oracle's lif6 raster through fc7, a SuperSpike lif7, the LI readout and the loss -> d loss / d fc7"""
+    from tests._planes import li_fp64
+    w = w7.to(dtype).clone().requires_grad_()
+    cur = spk6[:T - 1].to(dtype) @ w.t()
+    if dtype == torch.float32:                                       # (dyadic weights: the currents are the oracle's, and so is a free-running fp32 lif7)
+        assert torch.equal(HG.lif_forward(cur.detach(), HG.REFERENCE), spk7.bool()), "the fp32 CPU evaluation does not reproduce lif7's raster"
+    z = HG.lif_forward_autograd(cur, HG.REFERENCE, 100.0, forced=spk7)     # teacher-forced, as the backward under test is
+    out = _li_torch(z, torch.cat([w_cls, w_box]).to(dtype), HG.REFERENCE, order, dtype)
+    if dtype == torch.float64:                                       # (the torch recursion is tests/_planes.li_fp64)
+        last, _ = li_fp64(spk7.numpy(), torch.cat([w_cls, w_box]), HG.REFERENCE.a, -HG.REFERENCE.b, order)
+        assert np.abs(out.detach().numpy() - last[T - 1]).max() <= 1e-12
+    loss(out[:, :KCLS], out[:, KCLS:]).backward()
+    return w.grad
+
+
+def _roi_inputs(dev, R, seed):
+    from snn_automotive_object_detection_amd.stock.roi_align import MultiScaleRoIAlign
+    g = torch.Generator().manual_seed(seed)
+    feats = {str(i): (torch.randn((2, C_IN, h, w), generator=g) * 2.0).to(dev) for i, (h, w) in enumerate([(24, 40), (12, 20), (6, 10), (3, 5)])}
+    boxes = []
+    for k in (R - R // 2, R // 2):
+        xy = torch.rand((k, 2), generator=g) * torch.tensor([120.0, 70.0])
+        wh = torch.exp(torch.rand((k, 2), generator=g) * 3.0 + 1.0)
+        boxes.append(torch.cat([xy, torch.minimum(xy + wh, torch.tensor([159.0, 95.0]))], dim=1).to(dev))
+    return MultiScaleRoIAlign(["0", "1", "2", "3"], 7, 2).assign(feats, boxes, [(96, 160)] * 2)
+
+
+def _module_case(dev, feed, R, T, precision="bf16x3"):
+    """the head, its call, and the oracle's trace on the same inputs; fc6 and fc7 on the dyadic grid of tests/_exact_grid.py"""
+    import snn_automotive_object_detection_amd as S
+    from oracle import snn_oracle as OR
+    from snn_automotive_object_detection_amd import ops
+    from tests import _exact_grid as G
+    seed = 300 + R + T
+    if feed == "rows":
+        case = G.det_case(R, C_IN, HD, KCLS, T, seed)
+        w6, w7, w_cls, w_box, tr, x = case["w6"], case["w7"], case["w_cls"], case["w_bbox"], case["trace"], case["x"].to(dev)
+        call = lambda mod: mod(x)
+    else:
+        torch.manual_seed(seed)
+        d0 = S.FastRCNNPredictorSNNFull(C_IN * 49, HD, KCLS, T)
+        w6, w7 = G._grid(d0.fc6.weight.detach().clone(), "wide", seed, {}), G._grid(d0.fc7.weight.detach() * 3.0, "wide", seed + 1, {})
+        w_cls, w_box = d0.cls_score.weight.detach().clone(), d0.bbox_pred.weight.detach().clone()
+        flist, scales, rois, lvl = _roi_inputs(dev, R, seed)
+        p = ops.make_params(d0.p_enc, d0.p_lif)
+        _, pooled = ops.roi_align_encode(flist, scales, rois[:, 1:5], rois[:, 0], lvl, T, p, want_pooled=True)
+        with torch.no_grad():
+            _, _, tr = OR.det_head_forward(pooled.cpu().view(R, C_IN, 7, 7), w6, w7, w_cls, w_box, T, trace=True)
+        call = lambda mod: mod.forward_roialign(flist, scales, rois, lvl)
+    d = S.FastRCNNPredictorSNNFull(C_IN * 49, HD, KCLS, T).to(dev)
+    d.precision = precision
+    d.load_state_dict({"fc6.weight": w6, "fc7.weight": w7, "cls_score.weight": w_cls, "bbox_pred.weight": w_box})
+    return d, call, tr, (w7, w_cls, w_box)
+
+
+# (the last two: the pass on the fp32 matrix cores, whose backward recomputes the currents with snn_spike_gemm instead of snn_spike_gemm_bf16x3)
+MODULE_CASES = [(feed, R, T, "bf16x3") for T in (6, 12) for R in (37, 130) for feed in ("rows", "roialign")] + [("rows", 37, 12, "f32"), ("roialign", 130, 6, "f32")]
+
+
+@pytest.mark.parametrize("feed,R,T,precision", MODULE_CASES, ids=["%s_R%d_T%d_%s" % c for c in MODULE_CASES])
+def test_train_fc7_on_a_dyadic_head_with_zero_flips(gpu_device, feed, R, T, precision):
+    from snn_automotive_object_detection_amd import hidden, losses, ops
+    dev = gpu_device
+    d, call, tr, (w7, w_cls, w_box) = _module_case(dev, feed, R, T, precision)
+    spk6, spk7 = tr["spk6"], tr["spk7"]
+    plain = call(d)
+    assert all(t.grad_fn is None and not t.requires_grad for t in plain), "default off: the outputs carry no graph"
+    plain = [t.clone() for t in plain]
+    d.train_fc7 = True
+    with torch.no_grad():
+        assert all(not t.requires_grad for t in call(d)), "no grad mode: the plain forward"
+    outs = call(d)
+    sv = outs[0].grad_fn.saved
+    assert d._resolve_precision() == precision and sv.gemm is (ops.spike_gemm_bf16x3 if precision == "bf16x3" else ops.spike_gemm)
+    # precondition: the tapped rasters are the oracle's (it fails otherwise: nothing below would mean anything)
+    z6, z7 = HG.unpack_bits(sv.z6, HD), HG.unpack_bits(sv.z7, HD)
+    assert z6.shape == (T - 1, R, HD) and z7.shape == (T, R, HD)
+    assert torch.equal(z6, spk6[:T - 1].bool()), "lif6's saved rows differ from the oracle's raster in %d places" % int((z6 != spk6[:T - 1].bool()).sum())
+    assert torch.equal(z7, spk7.bool()), "lif7's saved rows differ from the oracle's raster in %d places" % int((z7 != spk7.bool()).sum())
+    assert bool(z6.any()) and bool(z7.any()), "a hidden layer is silent: the case proves nothing"
+    for got, want in zip(outs, plain):
+        assert got.requires_grad and torch.equal(got.detach(), want), "train_fc7 changed an output"
+    g = torch.Generator().manual_seed(R + T)
+    labels = torch.randint(0, KCLS, (R,), generator=g)
+    targets = torch.randn((R, 4), generator=g) * 0.5
+    for kind in ("fastrcnn", "quadratic"):
+        cpu_loss = _loss_of(kind, labels, targets)
+        if kind == "fastrcnn":
+            gpu_loss = lambda cls, box: sum(losses.fastrcnn_loss(cls, box, [labels.to(dev)], [targets.to(dev)]))
+        else:
+            gpu_loss = cpu_loss
+        for q in d.parameters():
+            q.grad = None
+        d.train_fc7, d.train_readout = True, False
+        outs = call(d)
+        gpu_loss(*outs).backward()
+        assert d.fc6.weight.grad is None, "fc6 received a gradient"
+        g7, g_cls, g_box = d.fc7.weight.grad.clone(), d.cls_score.weight.grad.clone(), d.bbox_pred.weight.grad.clone()
+        # the two readout gradients: what train_readout alone returns, bit for bit
+        for q in d.parameters():
+            q.grad = None
+        d.train_fc7, d.train_readout = False, True
+        gpu_loss(*call(d)).backward()
+        assert d.fc7.weight.grad is None
+        assert torch.equal(g_cls, d.cls_score.weight.grad) and torch.equal(g_box, d.bbox_pred.weight.grad), "readout gradients differ from the train_readout path"
+        # fc7.weight.grad against fp64 autograd, 4 x the error of fp32 CPU autograd
+        ref64 = _cpu_fc7_grad(spk6, spk7, w7, w_cls, w_box, T, "jump_first", cpu_loss, torch.float64)
+        ref32 = _cpu_fc7_grad(spk6, spk7, w7, w_cls, w_box, T, "jump_first", cpu_loss, torch.float32)
+        assert g7.shape == (HD, HD) and bool(torch.isfinite(g7).all()) and float(ref64.abs().max()) > 0
+        (gmax, grms), (cmax, crms) = HG.errors(g7.cpu(), ref64), HG.errors(ref32, ref64)
+        _note("fc7.weight.grad", max(gmax / (4 * cmax), grms / (4 * crms)))
+        print("%s R %d T %d %s: fc7 grad |err| max %.3g rms %.3g of |g| %.3g; fp32 CPU autograd %.3g / %.3g; error / tolerance %.3f (max) %.3f (rms)"
+              % (feed, R, T, kind, gmax, grms, float(ref64.abs().max()), cmax, crms, gmax / (4 * cmax), grms / (4 * crms)))
+        assert gmax <= 4 * cmax and grms <= 4 * crms
+    assert "Fc7Grad" in type(outs[0].grad_fn).__name__ and hidden.Fc7Grad is not None
+
+
+def test_train_fc7_refusals_on_the_device(gpu_device):
+    import snn_automotive_object_detection_amd as S
+    d = S.FastRCNNPredictorSNNFull(8 * 49, 32, 3, 2).to(gpu_device)
+    d.train_fc7 = True
+    x = torch.randn(5, 8, 7, 7, device=gpu_device)
+    with pytest.raises(ValueError, match="num_steps >= 3"):
+        d(x)
+    d.num_steps = 4
+    d.fc7.weight.requires_grad_(False)
+    assert all(t.grad_fn is None for t in d(x)), "fc7 frozen and train_readout off: the plain forward"
+    d.train_readout = True
+    assert "ReadoutGrad" in type(d(x)[0].grad_fn).__name__, "fc7 frozen: the readout graph alone"
+
+
+# ---- 5. graph capture ---------------------------------------------------------------------------------------------------------------------------
+def test_the_backward_chain_replays_bit_equal_on_two_data_sets(gpu_device):
+    from snn_automotive_object_detection_amd import hidden, ops
+    L = _L()
+    dev, R, Hd, Tc = gpu_device, 130, 96, 7
+    W = (Hd + 31) // 32
+    c = HG.REFERENCE
+    p = _params(c)
+    w7 = (torch.randn((Hd, Hd), generator=torch.Generator().manual_seed(1)) * 0.3).to(dev)
+    w7p = ops.pack_linear_bf16x3(w7)
+    v6 = L.snn_planes_view(64, R * W + 3, R, W, TP.WORD_MAJOR, Tc, 0)
+    v7 = L.snn_planes_view(0, R * W, R, W, TP.ROWS, Tc + 1, 0)
+    sets = []
+    for seed in (0, 1):
+        rng = np.random.default_rng(seed)
+        z6 = HG.pack_bits(torch.from_numpy(rng.random((Tc, R, Hd)) < 0.3)).numpy().view(np.uint32)
+        flat = np.full(16 + Tc * (R * W + 3), 0xa5a5a5a5, dtype=np.uint32)
+        idx = TP.word_index(TP.WORD_MAJOR, R, W)
+        for t in range(Tc):
+            flat[16 + t * (R * W + 3) + idx] = z6[t]
+        z7 = HG.pack_bits(torch.from_numpy(rng.random((Tc + 1, R, Hd)) < 0.3))
+        sets.append((torch.from_numpy(flat.view(np.uint8).copy()), z7.reshape(-1).view(torch.uint8).clone(),
+                     torch.from_numpy(rng.standard_normal((R, Hd)).astype(np.float32))))
+
+    def fn(ws6, ws7, gu):
+        a = hidden.planes_to_rows(ws6, v6, Tc)
+        z = hidden.planes_to_rows(ws7, v7, Tc + 1)
+        cur = ops.spike_gemm_bf16x3(a.view(Tc * R, W), Hd, Hd, w7p)
+        d_cur = hidden.lif_surrogate_bwd(cur.view(Tc, R, -1), z, Hd, p, 100.0, gu=gu)
+        return a, z, d_cur, hidden.spike_linear_wgrad(a, d_cur, Hd, Hd)
+    cap = GC.run_protocol(GC.FnCase(("spike_gemm_bf16x3",), dev, sets, fn), GC.HipGraph())
+    assert cap.n_replays == 4
+
+
+# ---- 6. one fine-tuning step end to end -------------------------------------------------------------------------------------------------------------
+def test_one_fine_tuning_step_moves_fc7_on_the_device(gpu_device):
+    from snn_automotive_object_detection_amd import hidden
+    from tests._small_model import small_model, targets as _targets
+    dev = gpu_device
+    model = small_model(dev)
+    det = model.roi_heads.box_head_and_predictor
+    det.train_fc7 = True
+    params = hidden.freeze_below_fc7(model)
+    assert len(params) == 5 and params[0] is det.fc7.weight
+    images = [torch.rand((3, 64, 64), generator=torch.Generator().manual_seed(i)).to(dev) for i in range(2)]
+    targets = _targets(dev)
+    gen = lambda: torch.Generator(device=dev).manual_seed(5)
+    with torch.no_grad():
+        first = [t.clone() for t in model.roi_heads.box_head_and_predictor(torch.ones(3, 32, 7, 7, device=dev))]
+    out = model.readout_losses(images, targets, generator=gen())
+    sum(out.values()).backward()
+    ids = {id(q) for q in params}
+    assert all(q.grad is None for q in model.parameters() if id(q) not in ids), "a parameter below fc7 received a gradient"
+    assert all(q.grad is not None and bool(torch.isfinite(q.grad).all()) for q in params)
+    assert float(det.fc7.weight.grad.abs().max()) > 0, "fc7 received a zero gradient: the case proves nothing"
+    before = det.fc7.weight.detach().clone()
+    torch.optim.SGD(params, lr=0.5).step()
+    assert not torch.equal(det.fc7.weight.detach(), before), "the optimiser step did not move fc7.weight"
+    with torch.no_grad():                                            # the next forward repacks fc7 (the caches key on the version counter)
+        second = model.roi_heads.box_head_and_predictor(torch.ones(3, 32, 7, 7, device=dev))
+    assert not all(torch.equal(a, b) for a, b in zip(first, second)), "the outputs did not move after the step"
+    again = model.readout_losses(images, targets, generator=gen())
+    assert all(bool(torch.isfinite(v)) for v in again.values())
+
+
+def test_log_the_largest_ratios():
+    """runs last in the file: the figures profiles/fc7_grad.txt and DESIGN.md 4.15 record"""
+    for k, v in sorted(RATIOS.items()):
+        print("largest error / tolerance ratio, %s: %.4f" % (k, v))
