@@ -164,6 +164,38 @@ def draw_currents(Tc: int, R: int, N: int, ldc: int, rate: float, c: Consts, see
     return cur
 
 
+def spike_rows(Tp, rows, K, density, rng):
+    """(int32 [T', rows, ceil(K / 32)] with the padding bits SET, float64 [T' rows, K])"""
+    z = torch.from_numpy(rng.random((Tp, rows, K)) < density)
+    return pack_bits(z, set_padding=True), z.reshape(Tp * rows, K).double().numpy()
+
+
+def padded(d: torch.Tensor, ldd: int) -> torch.Tensor:
+    """fp32 [T', rows, N] -> [T', rows, ldd] with NaN in the padding columns"""
+    out = torch.full(d.shape[:2] + (ldd,), float("nan"), dtype=torch.float32)
+    out[:, :, :d.shape[2]] = d
+    return out
+
+
+def exact_wgrad_case(rows, K, N, Tp, density, acc, seed) -> dict:
+    """the integer grid of snn_spike_linear_wgrad: gradients are integer numbers of units 2^-10 with |units| <= 128, so every sum over the
+    M = T' rows reduction rows, in any order, stays below 2^24 units and the float64 expectation must come back bit for bit.
+    a_rows int32 [T', rows, ceil(K / 32)] (padding bits set), d fp32 [T', rows, N], prior fp32 [N, K] (what accumulate = 1 adds to; drawn
+    either way), want32 fp32 [N, K]"""
+    rng = np.random.default_rng(seed)
+    a_rows, bits = spike_rows(Tp, rows, K, density, rng)
+    units = rng.integers(-128, 129, size=(Tp, rows, N))
+    assert Tp * rows * 128 + 64 < 2 ** 24                            # every sum, in any order, stays below 2^24 units of 2^-10
+    d = torch.from_numpy((units * 2.0 ** -10).astype(np.float32))
+    want = units.reshape(Tp * rows, N).astype(np.float64).T @ bits    # exact in float64
+    prior = rng.integers(-64, 65, size=(N, K)).astype(np.float64)
+    if acc:
+        want = want + prior
+    want32 = (want * 2.0 ** -10).astype(np.float32)
+    assert np.array_equal(want32.astype(np.float64), want * 2.0 ** -10)
+    return dict(a_rows=a_rows, d=d, prior=torch.from_numpy((prior * 2.0 ** -10).astype(np.float32)), want32=want32)
+
+
 def errors(got: torch.Tensor, ref64: torch.Tensor):
     """(largest absolute error, rms error) against the fp64 yardstick"""
     d = got.to(torch.float64) - ref64

@@ -13,7 +13,11 @@ asserts that the guards still hold GUARD_BYTE and that the interior behind the l
 (written zeros cannot be told from the fill 0x00: the other two fills show an overhang of any value).
 
 tests/test_ws_state_cpu.py proves on fake calls that the harness flags a read before a write, a write past the end and a flag left
-behind, and pins ENTRIES to the call sites of ops.py; tests/test_gpu_ws_state.py runs every entry of ENTRIES."""
+behind, and pins ENTRIES to the call sites of ops.py; tests/test_gpu_ws_state.py runs every entry of ENTRIES.
+
+The same contract for the OPERANDS of a call: `guarded` / `GuardedCall` / `run_input_guards` below put every input and output of one call into an
+allocation of its own, [guard | payload | guard] to the byte.  tests/_train_entries.py runs the seven training entries that way, with
+GuardedWorkspaces at readout._WS_WGRAD, hidden._WS_WGRAD and losses._WS_LOSS (tests/test_train_entries_cpu.py, tests/test_gpu_train_entries.py)."""
 import ast
 import contextlib
 import inspect
@@ -212,6 +216,144 @@ def still_poisoned(t: torch.Tensor) -> bool:
     if not t.numel():
         return True
     return bool(torch.isnan(t).all()) if t.is_floating_point() else bool((t.contiguous().reshape(-1).view(torch.uint8) == OUT_POISON).all())
+
+
+# ---- guarded operands: the same contract for the inputs and outputs of a call (tests/_train_entries.py) ----------------------------------
+OPERAND_GUARD = 64 << 10                # bytes of each guard around an operand: more than a work-group's stride at any shape the tests run
+OPERAND_ALIGN = 256                     # the payload starts on a multiple of this: no entry sees a base pointer it would refuse
+
+
+class Guarded:
+    """one allocation laid out [front guard | payload | back guard]: the payload is a contiguous view of exactly `shape`, starts 256-byte
+    aligned and touches both guards to the byte, so an element before the first or behind the last is a guard byte.  The wrappers take such
+    a view as it is (a contiguous tensor is never copied).  An OUTPUT is poison()ed: payload NaN / OUT_POISON, guards GUARD_BYTE.  An INPUT
+    is load()ed: payload = the source, guards a byte of the caller's choosing - 0x00 and 0xff (NaN as a float, every spike bit of a plane
+    word set, label -1) give different results to a kernel that reads one element too far."""
+
+    def __init__(self, shape, dtype, device):
+        self.shape, self.dtype = tuple(int(x) for x in shape), dtype
+        self.item = torch.empty((), dtype=dtype).element_size()
+        n = self.item
+        for x in self.shape:
+            n *= x
+        raw = torch.empty(2 * OPERAND_GUARD + n + OPERAND_ALIGN, dtype=torch.uint8, device=device)
+        lead = (-(raw.data_ptr() + OPERAND_GUARD)) % OPERAND_ALIGN
+        self.front = raw[lead:lead + OPERAND_GUARD]
+        self.bytes = raw[lead + OPERAND_GUARD:lead + OPERAND_GUARD + n]
+        self.back = raw[lead + OPERAND_GUARD + n:lead + 2 * OPERAND_GUARD + n]
+        self.payload = self.bytes.view(dtype).view(self.shape)
+        assert self.payload.is_contiguous() and (self.front.data_ptr() + OPERAND_GUARD) % OPERAND_ALIGN == 0
+        assert self.front.data_ptr() + OPERAND_GUARD + n == self.back.data_ptr()
+        assert not n or self.payload.data_ptr() == self.front.data_ptr() + OPERAND_GUARD       # (an empty tensor has no address)
+        self.guard_byte: Optional[int] = None
+        self.source: Optional[torch.Tensor] = None         # host bytes of what load() put into the payload
+
+    def set_guards(self, byte: int) -> None:
+        self.guard_byte = int(byte)
+        self.front.fill_(self.guard_byte)
+        self.back.fill_(self.guard_byte)
+
+    def poison(self) -> "Guarded":
+        if self.bytes.numel():
+            if self.payload.is_floating_point():
+                self.payload.fill_(float("nan"))
+            else:
+                self.bytes.fill_(OUT_POISON)
+        self.set_guards(GUARD_BYTE)
+        return self
+
+    def load(self, src: torch.Tensor, guard_byte: int) -> "Guarded":
+        src = src.detach().contiguous()
+        assert tuple(src.shape) == self.shape and src.dtype == self.dtype, (tuple(src.shape), src.dtype, self.shape, self.dtype)
+        self.payload.copy_(src)
+        self.source = src.cpu().reshape(-1).view(torch.uint8).clone() if src.numel() else torch.zeros(0, dtype=torch.uint8)
+        self.set_guards(guard_byte)
+        return self
+
+    def check_guards(self, what: str) -> None:
+        assert self.guard_byte is not None, "check_guards() before poison() / load()"
+        b = GuardedWorkspace._first_bad(self.back, self.guard_byte)
+        assert b is None, "%s: back guard touched at payload end + %d (payload %s, %d bytes)" % (what, b, self.shape, self.bytes.numel())
+        f = GuardedWorkspace._first_bad(self.front, self.guard_byte)
+        assert f is None, "%s: front guard touched at payload start - %d (payload %s)" % (what, OPERAND_GUARD - f, self.shape)
+
+    def check_unchanged(self, what: str) -> None:
+        """an input still holds what load() put there"""
+        now = self.bytes.cpu()
+        d = (now != self.source).nonzero()
+        assert not d.numel(), "%s: the call wrote into its input, first at byte %d of %d" % (what, int(d[0]), now.numel())
+
+    def unwritten(self) -> int:
+        """how many payload elements still hold the poison (NaN; every byte OUT_POISON)"""
+        if not self.bytes.numel():
+            return 0
+        if self.payload.is_floating_point():
+            return int(torch.isnan(self.payload).sum())
+        return int((self.bytes.view(-1, self.item) == OUT_POISON).all(dim=1).sum())
+
+
+def guarded(shape, dtype, device) -> Guarded:
+    """[front guard | payload | back guard] for one operand; `.payload` is the tensor a call is given"""
+    return Guarded(shape, dtype, device)
+
+
+class GuardedCall:
+    """the operands of ONE call, each in an allocation of its own.
+    inputs  {name: host tensor | None}: loaded flush between guards of `in_guard` bytes;
+    outputs {name: (shape, dtype) | host tensor | None}: a (shape, dtype) is poisoned and must come back wholly written; a host tensor is
+            what the call adds to (accumulate = 1: every element counts as written before the call).
+    verify() -> the snapshot of every output, after: no guard byte of any operand changed, no input changed, no output element left unwritten."""
+
+    def __init__(self, device, inputs: dict, outputs: dict, in_guard: int = 0x00):
+        self.g_in: Dict[str, Guarded] = {}
+        self.g_out: Dict[str, Guarded] = {}
+        self.prior = set()
+        for k, v in inputs.items():
+            if v is not None:
+                self.g_in[k] = guarded(v.shape, v.dtype, device).load(v, in_guard)
+        for k, v in outputs.items():
+            if v is None:
+                continue
+            if isinstance(v, torch.Tensor):
+                self.g_out[k] = guarded(v.shape, v.dtype, device).load(v, GUARD_BYTE)
+                self.prior.add(k)
+            else:
+                self.g_out[k] = guarded(v[0], v[1], device).poison()
+        self.ins = {k: (self.g_in[k].payload if k in self.g_in else None) for k in inputs}
+        self.outs = {k: (self.g_out[k].payload if k in self.g_out else None) for k in outputs}
+
+    def check_guards(self) -> None:
+        for k, g in self.g_out.items():
+            g.check_guards("output %s" % k)
+        for k, g in self.g_in.items():
+            g.check_guards("input %s" % k)
+            g.check_unchanged("input %s" % k)
+
+    def verify(self):
+        self.check_guards()
+        for k, g in self.g_out.items():
+            if k not in self.prior:
+                n = g.unwritten()
+                assert n == 0, "output %s: %d of %d elements were never written" % (k, n, g.payload.numel())
+        return snapshot(*[g.payload for g in self.g_out.values()])
+
+    def outputs_untouched(self) -> bool:
+        """after a refused call: every poisoned output is still poison, every prior still the prior"""
+        for k, g in self.g_out.items():
+            if k in self.prior:
+                if not torch.equal(g.bytes.cpu(), g.source):
+                    return False
+            elif not still_poisoned(g.payload):
+                return False
+        return True
+
+
+def run_input_guards(call):
+    """call(in_guard) -> snapshot, under input guards of zeros and of 0xff bytes: what lies behind (or before) an input must not reach a
+    result; -> the snapshot"""
+    a, b = call(0x00), call(0xff)
+    assert same_bits(a, b), "input guards 0xff against 0x00: %s" % first_difference(a, b)
+    return a
 
 
 # ---- the entries: every public ops function that takes a workspace, with the variants tests/test_gpu_ws_state.py runs ---------------------
