@@ -827,6 +827,45 @@ int snn_spike_linear_wgrad(const uint32_t* a_rows /* [T'][rows][ceil(K/32)] */, 
                            int T_prime, int64_t rows, int K, int N, float* gw /* [N][K] */, int accumulate, void* scratch,
                            size_t scratch_bytes, snn_stream_t stream);
 
+/* ---- fc6's gradient: the spike-fed weight gradient on the bf16 matrix cores --------------------------------------------
+ * One layer below the section above: lif6's upstream gradient is gz6_t = d_cur7_t W7 (t <= T - 2, no gu term), lif6 receives cur6_t =
+ * W6 enc_t of which only steps 0 .. T - 3 matter (Tc = T - 2: the window the forward forms, see the spike taps), and
+ *     dL/dW6[n][k] = sum_{t <= T - 3} sum_r d_cur6_t[r][n] enc_t(r, k)        k = channel * 49 + bin, fc6.weight's own layout.
+ * snn_lif_surrogate_bwd (gz given, gu null), snn_planes_to_rows, the un-fused spike GEMMs and the stand-alone encoders serve it as they are;
+ * what fc6's shape (K = 49 C = 12544, N = 1024, M = (T - 2) R = 10240) needs is a weight gradient that takes K > 8192, a scratch that does
+ * not grow with slabs the grid does not need, and the bf16 matrix cores:
+ *
+ * snn_spike_wgrad_bf16x3: gw[n][k] (+)= sum_{t < T'} sum_r d_cur[t][r][n] * bit_t(r, k), the argument list of snn_spike_linear_wgrad.
+ *   - 1 <= K <= 16384 (49 C up to C = 320), 1 <= N <= 8192, rows < 2^31, T' <= SNN_MAX_STEPS, N <= ldd < 2^28; K need not be a multiple of
+ *     32; rows past `rows`, columns past N and bits past K contribute nothing, no word past a row's last word is loaded and no byte outside
+ *     gw [N][K] is written;
+ *   - every d_cur element is split on the fly, once per work-group, into three bf16 values hi = rn(x), mid = rn(x - hi), lo = rn(x - hi - mid)
+ *     - exact for every fp32 of magnitude below 2^128 - 2^119 (above it hi rounds up to bf16 infinity) whose lowest set bit is >= 2^-133
+ *     (k_bf16x3_split_check describes the same split) - the spike operand is
+ *     0.0 / 1.0 in bf16, every product is exact, a result is an fp32 accumulation of exact products inside v_mfma_f32_32x32x16_bf16; the planes
+ *     reach an accumulator in the order lo, mid, hi, so a column with a single spike returns d_cur bit for bit (-0 may return +0);
+ *   - PRECONDITION: d_cur is finite and of magnitude below 2^128 - 2^119 = 0x7F7F8000 (bf16's largest value plus half its last place).  An
+ *     element at or above it, infinite or NaN makes its whole output row non-finite (as 0 x inf does in the fp32 kernel);
+ *   - DETERMINISTIC: the T' x rows reduction rows are split into slabs, a pure function of (M = T' rows, K, N): with tiles = ceil(N / 128)
+ *     ceil(K / 256), want = 1 if tiles >= 256, else min(ceil(256 / tiles), ceil(M / 256), 32); a slab holds ceil(ceil(M / want) / 32) 32 rows.
+ *     One slab (the output tiles alone fill the 256 CUs): the kernel writes (accumulate = 0) or adds to (1) every element of gw itself.
+ *     Several: partial tiles go to `scratch`, a second launch adds them in ascending order and writes or adds to every element of gw;
+ *   - snn_spike_wgrad_bf16x3_workspace_bytes = 4 min(min(ceil(M / 256), 32) N K, 256 x 128 x 256 + N K): never below slabs N K floats,
+ *     monotone in every argument (the slab count itself falls as the tiles grow), 0 outside the limits, non-zero inside; at fc6's shape
+ *     (rows 1024, T' 10, K 12544, N 1024) it is 85 MB, below 2 N K floats.  The entry asks for the queried size whatever the plan: with ONE
+ *     slab (fc6's shape) no byte of scratch is read or written - what monotonicity costs;
+ *   - snn_spike_wgrad_bf16x3_slabs: that plan's slab count and, through `slab_rows`, the rows of every slab but the last; host only, 0 outside
+ *     the limits;
+ *   - rounding: against exact arithmetic every element is within (3 T' rows + slabs + 4) 2^-24 sum_{t, r} |d_cur[t][r][n]| bit_t(r, k)
+ *     + T' rows 2^-133: the three planes' terms, each |part| <= |d|, under the standard model, and what lies below the finest bf16 subnormal.
+ *   One or two launches; the contract of the section above (stream-only, capturable, no floating-point atomics, no memset, bit-equal
+ *   repeats, -1 with snn_last_error before any device work). */
+size_t snn_spike_wgrad_bf16x3_workspace_bytes(int64_t rows, int K, int N, int T_prime);
+int snn_spike_wgrad_bf16x3_slabs(int64_t rows, int K, int N, int T_prime, int64_t* slab_rows /* nullable */);
+int snn_spike_wgrad_bf16x3(const uint32_t* a_rows /* [T'][rows][ceil(K/32)] */, const float* d_cur /* [T'][rows][ldd] */, int ldd,
+                           int T_prime, int64_t rows, int K, int N, float* gw /* [N][K] */, int accumulate, void* scratch,
+                           size_t scratch_bytes, snn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

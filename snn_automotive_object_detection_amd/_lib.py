@@ -238,6 +238,11 @@ SYMBOLS = {
     "snn_spike_linear_wgrad_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
     "snn_spike_linear_wgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_size_t, c_stream]),
+    # the spike-fed weight gradient on the bf16 matrix cores (fc6_grad.py): the argument lists of the fp32 pair above
+    "snn_spike_wgrad_bf16x3_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "snn_spike_wgrad_bf16x3_slabs": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "snn_spike_wgrad_bf16x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_size_t, c_stream]),
 }
 
 _LIB = None
@@ -250,7 +255,9 @@ _STATIC_PATH = ("snn_roi_assign", "snn_det_postprocess_padded", "snn_pack_padded
                 "snn_match_targets_workspace_bytes", "snn_match_targets", "snn_rpn_loss_grad_workspace_bytes", "snn_rpn_loss_grad",
                 "snn_det_loss_grad_workspace_bytes", "snn_det_loss_grad",
                 # (... from before the hidden-layer gradients: hidden.py then raises AttributeError)
-                "snn_planes_to_rows", "snn_lif_surrogate_bwd", "snn_spike_linear_wgrad_workspace_bytes", "snn_spike_linear_wgrad")
+                "snn_planes_to_rows", "snn_lif_surrogate_bwd", "snn_spike_linear_wgrad_workspace_bytes", "snn_spike_linear_wgrad",
+                # (... from before fc6's gradient: fc6_grad.py then raises AttributeError)
+                "snn_spike_wgrad_bf16x3_workspace_bytes", "snn_spike_wgrad_bf16x3_slabs", "snn_spike_wgrad_bf16x3")
 
 
 class SnnHipError(RuntimeError):

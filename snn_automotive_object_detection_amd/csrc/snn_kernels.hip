@@ -162,6 +162,7 @@ __global__ void k_pack_heads(const float* __restrict__ wa, int NA, const float* 
 #include "snn_wgrad.h"
 #include "snn_loss.h"
 #include "snn_hidden.h"
+#include "snn_spike_wgrad_x3.h"
 
 // ================================================================================================
 // C ABI
@@ -3498,6 +3499,66 @@ int snn_spike_linear_wgrad(const uint32_t* a_rows, const float* d_cur, int ldd, 
     hipLaunchKernelGGL(k_spike_wgrad_reduce, dim3((unsigned)min(cdivll((long long)n, 256), 1LL << 20)), dim3(256), 0, s, (const float*)scratch, a.n_slabs, n, gw,
                        accumulate);
     SNN_CHECK_LAUNCH("k_spike_wgrad_reduce");
+    return 0;
+}
+
+// ---- the spike-fed weight gradient on the bf16 matrix cores: d_cur split into three bf16 planes on the fly (kernels:
+// snn_spike_wgrad_x3.h) ----
+static int wgrad3_shape_ok(long long rows, int K, int N, int T) {
+    return rows >= 1 && rows <= 0x7fffffffLL && K >= 1 && K <= W3_MAX_K && N >= 1 && N <= W3_MAX_N && T >= 1 && T <= SNN_MAX_STEPS;
+}
+// row slabs of the reduction over M = T' x rows: a pure function of (M, K, N) - one when the output tiles alone fill the device, otherwise
+// as many as it takes to fill it; every slab but the last holds slab_rows rows (a multiple of the stage)
+static int wgrad3_slabs(long long M, int K, int N, long long* slab_rows) {
+    const long long tiles = (long long)cdiv(N, W3_TN) * cdiv(K, W3_TK);
+    const long long want = tiles >= W3_FILL ? 1 : min(min(cdivll(W3_FILL, tiles), cdivll(M, W3_SLAB_ROWS)), (long long)W3_MAX_SLABS);
+    const long long per = cdivll(cdivll(M, want), W3_MB) * W3_MB;
+    if (slab_rows) *slab_rows = per;
+    return (int)cdivll(M, per);
+}
+
+// slabs N K <= min(ceil(M / 256) capped at 32, 256 / tiles + 1) N K, and N K / tiles <= 128 x 256: both bounds are monotone in every argument
+// (the slab count itself is not: it falls as the tiles grow), so their minimum is
+size_t snn_spike_wgrad_bf16x3_workspace_bytes(int64_t rows, int K, int N, int T_prime) {
+    if (!wgrad3_shape_ok(rows, K, N, T_prime)) return 0;
+    const size_t nk = (size_t)N * (size_t)K;
+    const size_t by_rows = (size_t)min(cdivll((long long)rows * T_prime, W3_SLAB_ROWS), (long long)W3_MAX_SLABS) * nk;
+    const size_t by_fill = (size_t)W3_FILL * W3_TN * W3_TK + nk;
+    return (by_rows < by_fill ? by_rows : by_fill) * sizeof(float);                 // (no min(): the device headers' overloads narrow to int)
+}
+
+// the launch plan's slab count (and the rows of every slab but the last), host only: what the header documents, observable
+int snn_spike_wgrad_bf16x3_slabs(int64_t rows, int K, int N, int T_prime, int64_t* slab_rows) {
+    if (slab_rows) *slab_rows = 0;
+    if (!wgrad3_shape_ok(rows, K, N, T_prime)) return 0;
+    long long per = 0;
+    const int n = wgrad3_slabs((long long)rows * T_prime, K, N, &per);
+    if (slab_rows) *slab_rows = per;
+    return n;
+}
+
+int snn_spike_wgrad_bf16x3(const uint32_t* a_rows, const float* d_cur, int ldd, int T_prime, int64_t rows, int K, int N, float* gw, int accumulate,
+                           void* scratch, size_t scratch_bytes, snn_stream_t stream) {
+    if (!a_rows || !d_cur || !gw) return fail(-1, "snn_spike_wgrad_bf16x3: null planes, gradient or result");
+    if (!wgrad3_shape_ok(rows, K, N, T_prime))
+        return fail(-1, "snn_spike_wgrad_bf16x3: rows = %lld, K = %d, N = %d, T' = %d (1 <= rows < 2^31, 1 <= K <= %d, 1 <= N <= %d, 1 <= T' <= %d)",
+                    (long long)rows, K, N, T_prime, W3_MAX_K, W3_MAX_N, SNN_MAX_STEPS);
+    if (ldd < N || ldd >= (1 << 28)) return fail(-1, "snn_spike_wgrad_bf16x3: ldd = %d (N = %d <= ldd < 2^28)", ldd, N);
+    if (accumulate != 0 && accumulate != 1) return fail(-1, "snn_spike_wgrad_bf16x3: accumulate = %d (0 or 1)", accumulate);
+    const size_t need = snn_spike_wgrad_bf16x3_workspace_bytes(rows, K, N, T_prime);
+    if (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 3)) return fail(-1, "snn_spike_wgrad_bf16x3: scratch %zu < %zu bytes (or null / misaligned)", scratch_bytes, need);
+    Wgrad3Args a;
+    a.a = a_rows; a.d = d_cur; a.M = (long long)rows * T_prime; a.ldd = ldd; a.K = K; a.Kw = cdiv(K, 32); a.N = N; a.accumulate = accumulate;
+    a.n_slabs = wgrad3_slabs(a.M, K, N, &a.slab_rows);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_wgrad3_partial, dim3(cdiv(K, W3_TK), cdiv(N, W3_TN), a.n_slabs), dim3(256), 0, s, a, (float*)scratch, gw);
+    SNN_CHECK_LAUNCH("k_wgrad3_partial");
+    if (a.n_slabs > 1) {
+        const size_t n = (size_t)N * K;
+        hipLaunchKernelGGL(k_wgrad3_reduce, dim3((unsigned)min(cdivll((long long)n, 256), 1LL << 20)), dim3(256), 0, s, (const float*)scratch, a.n_slabs, n, gw,
+                           accumulate);
+        SNN_CHECK_LAUNCH("k_wgrad3_reduce");
+    }
     return 0;
 }
 

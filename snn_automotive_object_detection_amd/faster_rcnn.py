@@ -8,7 +8,7 @@ import os
 
 from torch import nn
 
-from . import hidden, ops, readout
+from . import fc6_grad, hidden, ops, readout
 from .rpn import _SpikingHead, _WeightCache, _pack_heads_unchecked, _per_precision
 
 
@@ -49,6 +49,8 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
                                            # forward_roialign carry a grad_fn to those two weights alone (readout.py); False: as ever
         self.train_fc7 = False             # True: in grad mode, with fc7.weight requiring grad, that grad_fn also reaches fc7.weight through a SuperSpike
                                            # lif7 (hidden.py; "bf16x3" / "f32" only, num_steps >= 3); False: as ever
+        self.train_fc6 = False             # True: in grad mode, with fc6.weight requiring grad, the grad_fn reaches fc6.weight as well, through SuperSpike
+                                           # lif7 and lif6 (fc6_grad.py; same limits); checked before train_fc7; False: as ever
         self.precision = "bf16x3"          # or "f32" (fp32 matrix cores) / "mxfp6" (fp4 x fp6 digit planes) / "bf16" (ONE bf16 weight plane: fc6, fc7
                                            # and the LI heads on w.to(torch.bfloat16) - outside the 1e-4-to-fp32 contract, as "mxfp6"); see RPNHeadSNN
         self.fc6 = nn.Linear(in_channels, representation_size, bias=False)          # :448
@@ -128,6 +130,11 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         return dict(fc6_route=route, fc6_crossover=self.fc6_crossover, route_stat=self.route_stat)
 
     def forward(self, x):
+        if self.train_fc6 and fc6_grad.wanted(self):
+            cls, bbox = self._forward(x)
+            R = int(cls.shape[0])
+            return self._attach_fc6(cls, bbox, R, int(x[0].numel()) if R else self.in_channels,
+                                    lambda steps, p: ops.encode_rows(x.flatten(start_dim=1), steps, p))
         if self.train_fc7 and hidden.wanted(self):
             cls, bbox = self._forward(x)
             R = int(cls.shape[0])
@@ -142,6 +149,11 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
         """Same head fed straight from the FPN maps: MultiScaleRoIAlign(7x7, sampling 2) is fused with the encoder
         (the [R,C,7,7] RoI features of roi_heads.py:1217 are never materialised).  rois [R,5] = (image, x1,y1,x2,y2) - or, with
         ``roi_batch`` (int32 [R], the image of every row: the table ops.roi_assign writes), rois [R,4]."""
+        if self.train_fc6 and fc6_grad.wanted(self):
+            cls, bbox = self._forward_roialign(feats, scales, rois, roi_level, roi_batch)
+            boxes, batch = (rois[:, 1:5], rois[:, 0]) if roi_batch is None else (rois, roi_batch)
+            return self._attach_fc6(cls, bbox, int(cls.shape[0]), int(feats[0].shape[1]) * 49,
+                                    lambda steps, p: ops.roi_align_encode(feats, scales, boxes, batch, roi_level, steps, p))
         if self.train_fc7 and hidden.wanted(self):
             cls, bbox = self._forward_roialign(feats, scales, rois, roi_level, roi_batch)
             return self._attach_fc7(cls, bbox, int(cls.shape[0]), int(feats[0].shape[1]) * 49)
@@ -182,6 +194,22 @@ class FastRCNNPredictorSNNFull(_SpikingHead):
                                                w6_inner=self.fc6_inner(prec), route=route, spike_rates=False)
                 ws = taps._current_ws(cls.device)
         return hidden.attach(self, (cls, bbox), ws, v6, v7, T, p, prec)
+
+    def _attach_fc6(self, cls, bbox, R: int, D: int, encode):
+        """_attach_fc7 one layer further down (fc6_grad.py): the grad_fn also leads to fc6.weight.  ``encode(steps, p)`` re-runs
+        the stand-alone encoder on the feed of the pass that just ran - the features are still alive here - for its first T - 2 steps"""
+        from . import taps
+        ws = v6 = v7 = None
+        T = int(self.num_steps)
+        with torch.no_grad():
+            prec = self._resolve_precision()
+            p = self._params(prec)
+            if R:
+                route = self.fc6_route if self.fc6_route is not None else os.environ.get("SNN_FC6_ROUTE", "sparse")
+                v6, v7 = taps.det_planes_views(R, D, self.representation_size, self.num_classes, int(self.bbox_pred.weight.shape[0]), T, p,
+                                               w6_inner=self.fc6_inner(prec), route=route, spike_rates=False)
+                ws = taps._current_ws(cls.device)
+        return fc6_grad.attach(self, (cls, bbox), ws, v6, v7, T, p, prec, lambda steps: encode(steps, p))
 
     @torch.no_grad()
     def _forward(self, x):

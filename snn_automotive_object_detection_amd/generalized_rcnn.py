@@ -85,7 +85,8 @@ class GeneralizedRCNN(nn.Module):
         loss_box_reg.  With ``train_readout`` on both heads (and readout.freeze_hidden) ``sum(losses.values()).backward()`` gives the four
         readout weights their exact gradients; nothing else receives one - unless the box predictor also has ``train_fc7`` set (with
         hidden.freeze_below_fc7): the detector head's outputs then carry a graph that reaches ``fc7.weight`` too, and the same
-        ``backward()`` leaves its SuperSpike gradient there (hidden.py).  Proposals are selected with the "training" entries of the
+        ``backward()`` leaves its SuperSpike gradient there (hidden.py); with ``train_fc6`` (and fc6_grad.freeze_below_fc6) the
+        graph reaches ``fc6.weight`` as well (fc6_grad.py).  Proposals are selected with the "training" entries of the
         RPN's two top-n dicts.  ``generator``: the torch.Generator of both samplers.  ``forward`` in training mode still raises."""
         if self.training:
             raise NotImplementedError("readout_losses runs in eval mode: model.train() is out of scope (DESIGN.md §7)")

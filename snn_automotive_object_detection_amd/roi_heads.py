@@ -213,7 +213,8 @@ class RoIHeadsSNN(nn.Module):
         fused RoIAlign path where ``forward`` takes it).  With ``train_readout`` on the head, grad mode on and a readout weight requiring
         grad, the two outputs carry a ``grad_fn`` (readout.py): a caller puts their own loss on them in eval mode and gets the exact
         gradients of ``cls_score.weight`` / ``bbox_pred.weight``; with ``train_fc7`` on the head and ``fc7.weight`` requiring grad the same
-        graph also reaches ``fc7.weight`` through a SuperSpike lif7 (hidden.py).  ``model.train()`` stays refused."""
+        graph also reaches ``fc7.weight`` through a SuperSpike lif7 (hidden.py), and with ``train_fc6`` and ``fc6.weight`` requiring grad
+        ``fc6.weight`` through lif6 as well (fc6_grad.py).  ``model.train()`` stays refused."""
         if self.training:
             raise NotImplementedError("inference only: training the RoI heads is out of scope (DESIGN.md §7)")
         pool, head = self.box_roi_pool, self.box_head_and_predictor
@@ -262,7 +263,8 @@ class RoIHeadsSNN(nn.Module):
         """the RoI heads' half of a readout fine-tuning step (roi_heads.py:1203-1245 in eval mode): select_training_samples,
         ``head_outputs`` on the sampled RoIs and losses.fastrcnn_loss -> {"loss_classifier", "loss_box_reg"}.  With ``train_readout`` on
         the head the two losses lead to cls_score.weight and bbox_pred.weight through autograd; with ``train_fc7`` on it (hidden.py; DESIGN.md
-        4.15) the head's outputs carry a graph that also reaches fc7.weight, and so do the two losses - no other code path is involved."""
+        4.15) the head's outputs carry a graph that also reaches fc7.weight, with ``train_fc6`` (fc6_grad.py) fc6.weight as well,
+        and so do the two losses - no other code path is involved."""
         from . import losses
         if self.training:
             raise NotImplementedError("head_losses runs in eval mode: training the RoI heads is out of scope (DESIGN.md §7)")
